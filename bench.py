@@ -14,13 +14,22 @@ default sampling (temperature 0.8, top-k 40, top-p 0.9, repeat penalty 1.1),
 EOS disabled so every trial produces the requested length.  ``value`` is the
 whole-job generated tokens/s; the JSON also reports measured GPU energy per
 generated token from the amd-smi counters (``J_per_token``; idle-subtracted
-variant too).  Baseline: the reference's llama3.1:8b on-device 1000-word cell,
+variant with ``--full``).  Baseline: the reference's llama3.1:8b on-device 1000-word cell,
 est. 19.2 tok/s and 0.574 J/token on a MacBook Pro M2.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--model M] [--words W] [--batch B (default 256)]
+                       [--dump-outputs DIR] [--full]
        (multi-GPU: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ..., or plain
        ``python bench.py --gpus N``, which spawns the N ranks itself before anything touches a GPU)
 
+A plain run sets up, warms up, times the ``--steps`` steps (GPU energy read over the same window) and prints the
+JSON line.  ``--dump-outputs DIR`` also writes what the last timed step returned to its caller: the generated token
+ids of every trial, ``DIR/tokens.npy`` (float32 [batch, tokens], -1 past a trial's end; ``tokens.rank<r>.npy``
+per rank on several GPUs).  Prompts, sampling seeds and random-init weights depend on the arguments only, so two
+builds can be compared token for token.
+
+``--full`` adds everything else, outside the timed region.  Before the steps: a ``--settle``, the idle-power
+baseline (``idle_power_W``, ``J_per_token_idle_subtracted``) and one more untimed step back to a warm state.
 After the timed steps and a ``--settle`` every rank also runs the reference's one-request-at-a-time protocol
 (batch 1; reference experiment/RunnerConfig.py:120-131): the median of ``--single-trials`` full-length
 generations, each in its own energy window, for the bench model on bf16 (``single_stream_tok_per_s`` /
@@ -105,8 +114,15 @@ def main() -> int:
                     help="KV-cache storage: bf16 (headline) or fp8 e4m3 (half the attention bytes; separate config)")
     ap.add_argument("--device", choices=("cuda", "cpu"), default="cuda",
                     help="cpu: the torch oracle backend over gloo (tests of the multi-rank plumbing; tiny models)")
-    ap.add_argument("--settle", type=float, default=8.0, help="seconds of rest before the idle-power baseline")
-    ap.add_argument("--no-single", action="store_true", help="skip the batch-1 (single-stream) measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's generated token ids to DIR/tokens.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the idle-power baseline and the batch-1 (single-stream) table; a plain run "
+                         "times the steps only")
+    ap.add_argument("--settle", type=float, default=8.0,
+                    help="--full: seconds of rest before the idle-power baseline")
+    ap.add_argument("--no-single", action="store_true",
+                    help="--full: skip the batch-1 (single-stream) measurement")
     ap.add_argument("--single-trials", type=int, default=3, help="batch-1 generations per (model, dtype); median")
     ap.add_argument("--single-settle", type=float, default=1.0, help="seconds of rest before each batch-1 trial")
     ap.add_argument("--single-models", default="qwen2:1.5b,gemma:2b",
@@ -123,6 +139,8 @@ def main() -> int:
     ap.add_argument("--w4a8-min-rows", type=int, default=0,
                     help="MXFP4: rows above which forwards run W4A8 instead of W4A16 (0: the runtime's default, 16)")
     ns = ap.parse_args()
+    if ns.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if ns.checkpoint:  # before any engine (and inherited by spawned ranks): --model's engines load the checkpoint
         os.environ["CAIN_CHECKPOINTS"] = ",".join(filter(None, [os.environ.get("CAIN_CHECKPOINTS", ""),
@@ -172,9 +190,11 @@ def main() -> int:
         return [f"In {ns.words} words, please give me information about {tps[(step * ns.batch + i + rank * 7) % len(tps)]}"
                 for i in range(ns.batch)]
 
+    last = []  # the latest step's results, as generate() returned them
+
     def one_step(step):
-        res = eng.generate(prompts(step), n_tok, [dict(opts, seed=step * 100003 + i + 1) for i in range(ns.batch)])
-        return sum(r.eval_count for r in res)
+        last[:] = eng.generate(prompts(step), n_tok, [dict(opts, seed=step * 100003 + i + 1) for i in range(ns.batch)])
+        return sum(r.eval_count for r in last)
 
     def sync():
         if not cpu:
@@ -195,14 +215,16 @@ def main() -> int:
             # host CPU + RAM energy is shared by every rank of the node: each rank is charged its share
             meter = EnergyMeter(devices=[local], period_ms=100.0, keep_samples=False, sources=("gpu", "cpu", "ram"),
                                 host_share=1.0 / int(os.environ.get("LOCAL_WORLD_SIZE", world)))
-            # the board stays ~15 % above its idle floor for seconds after a burst: settle first
-            sync()
-            time.sleep(max(0.0, ns.settle))
-            meter.measure_idle(2.0)
+            if ns.full:
+                # the board stays ~15 % above its idle floor for seconds after a burst: settle first
+                sync()
+                time.sleep(max(0.0, ns.settle))
+                meter.measure_idle(2.0)
         except Exception as exc:  # energy is auxiliary to the throughput metric
             print(f"[bench] energy meter unavailable: {exc}", file=sys.stderr)
             meter = None
-        one_step(-100)  # back to a warm steady state before the timed region
+        if ns.full:
+            one_step(-100)  # back to a warm steady state before the timed region
 
     def barrier():
         if world > 1:
@@ -220,6 +242,15 @@ def main() -> int:
     barrier()
     dt = time.perf_counter() - t0
     reading = meter.stop() if meter else None
+
+    if ns.dump_outputs:  # what the last timed step handed back: one row of generated token ids per trial
+        import numpy as np
+
+        toks_out = np.full((len(last), max(r.eval_count for r in last)), -1.0, dtype=np.float32)  # ids < 2**24: exact
+        for i, r in enumerate(last):
+            toks_out[i, :r.eval_count] = r.tokens
+        os.makedirs(ns.dump_outputs, exist_ok=True)
+        np.save(os.path.join(ns.dump_outputs, "tokens.npy" if world == 1 else f"tokens.rank{rank}.npy"), toks_out)
 
     # ---- batch 1, the reference's one-request-at-a-time protocol (outside the timed region): after a settle, the
     # median of --single-trials generations of the full request length per (model, weight dtype), each with its
@@ -254,7 +285,7 @@ def main() -> int:
         return statistics.median(rates), statistics.median(jpt)
 
     cases = []
-    if not ns.no_single:
+    if ns.full and not ns.no_single:
         cases = [(ns.model, "bf16")]
         if not cpu and ns.weights == "bf16":
             cases += [(ns.model, "fp8"), (ns.model, "fp4")]
@@ -308,6 +339,7 @@ def main() -> int:
             "n_gpus": world,
             "steps": ns.steps,
             "warmup": ns.warmup,
+            "full": ns.full,
             "ms_per_step": round(1000 * t_max / ns.steps, 2),
             "higher_is_better": True,
             "scaling": "weak",

@@ -41,6 +41,41 @@ def test_bench_rejects_mismatched_launcher():
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
 
 
+def test_bench_dumps_the_last_steps_tokens_and_repeats_them(tmp_path):
+    """--dump-outputs: the last timed step's generated ids as float32 [batch, tokens]; a second run with the same
+    arguments writes the same array (prompts, seeds and weights depend on the arguments only)."""
+    import numpy as np
+
+    arrays = []
+    for d in ("a", "b"):
+        r = _run(["--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _line(r.stdout)
+        assert [p.name for p in (tmp_path / d).iterdir()] == ["tokens.npy"]
+        arrays.append(np.load(tmp_path / d / "tokens.npy"))
+    a, b = arrays
+    assert a.dtype == np.float32 and a.shape == (2, line["config"]["seq_len"])
+    assert (a >= 0).all() and (a == np.floor(a)).all()
+    assert np.array_equal(a, b)
+
+
+def test_bench_single_stream_rows_need_full():
+    """A plain run times the steps only; --full also fills the batch-1 (single-stream) rows."""
+    args = [a for a in ARGS if a != "--no-single"] + ["--single-trials", "1", "--single-settle", "0", "--settle", "0"]
+
+    def run(extra):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py")] + extra + args, capture_output=True, text=True,
+                           timeout=240, env=dict(os.environ, OMP_NUM_THREADS="1"), cwd=str(ROOT))
+        assert r.returncode == 0, r.stderr[-2000:]
+        return _line(r.stdout)
+
+    plain, full = run([]), run(["--full"])
+    assert plain["full"] is False and plain["single_stream_tok_per_s"] is None and plain["single_stream_by_model"] == {}
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert full["full"] is True and full["single_stream_tok_per_s"] > 0
+    assert set(full["single_stream_by_model"]) == {"tiny-llama3.1:8b"}
+
+
 def test_bench_on_a_checkpoint(tmp_path):
     """--checkpoint: the bench model's engine loads a Hugging Face checkpoint (here a tiny one written by
     transformers) instead of random-init weights, and the JSON line says so."""

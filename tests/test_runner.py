@@ -20,7 +20,6 @@ from cain_amd.runner.store import CSVOutputManager, JSONOutputManager
 from cain_amd.runner.validator import ConfigValidator
 
 ROOT = Path(__file__).resolve().parent.parent
-REF_CONFIG = Path("/root/reference/experiment/RunnerConfig.py")
 
 STUDY_MODELS = ['llama3.1:8b', 'gemma:2b', 'gemma:7b', 'phi3:3.8b', 'qwen2:1.5b', 'qwen2:7b', 'mistral:7b']
 
@@ -346,20 +345,6 @@ def test_cli_help_config_create_dry_run(tmp_path):
     assert r.returncode == 0 and "dry run: 3 runs" in r.stdout  # 6 combos minus 3 excluded
     r = _cli("no-such-command")
     assert r.returncode == 1 and "not recognised" in r.stdout
-
-
-@pytest.mark.skipif(not REF_CONFIG.exists(), reason="reference checkout not mounted")
-def test_reference_config_loads_unchanged():
-    from cain_amd.runner.cli import build_config
-
-    EventSubscriptionController.clear()
-    cfg, md, _ = build_config(str(REF_CONFIG))
-    table = cfg.create_run_table_model().generate_experiment_run_table()
-    assert len(table) == 1260
-    assert list(table[0]) == ["__run_id", "__done", "model", "method", "length", "topic", "execution_time",
-                              "cpu_usage", "gpu_usage", "memory_usage", "codecarbon__energy_consumed"]
-    assert cfg.time_between_runs_in_ms == 90000
-    EventSubscriptionController.clear()
 
 
 def test_compat_modules_expose_reference_names():

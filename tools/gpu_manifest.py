@@ -77,7 +77,7 @@ SETS = {
     "r4_prune": [
         ("prune_tests", 900, f"{TEST} tests/test_wgemm_gpu.py tests/test_ops_gpu.py tests/test_w8a8_gpu.py "
                              f"tests/test_engine_gpu.py"),
-        ("bench", 400, f"{PY} bench.py --gpus 1 --steps 10 --warmup 3"),
+        ("bench", 400, f"{PY} bench.py --gpus 1 --steps 10 --warmup 3 --full"),
     ],
     # headline A/B, interleaved: the round-3 library (ab/libcain_kernels_head.so: unscaled fp16 slabs, before the
     # pruning), the tree without the slab scaling (ab/libcain_kernels_noscale.so) and the tree
@@ -107,14 +107,14 @@ SETS = {
                                  f"tests/test_continuous_gpu.py tests/test_energy_gpu.py tests/test_fullsize_gpu.py")],
     # round-end evidence: the driver's bench command, then kernel stats of the headline and of batch-1 fp4
     "r4_final": [
-        ("bench", 900, f"{PY} bench.py --gpus 1 --steps 20 --warmup 5"),
+        ("bench", 900, f"{PY} bench.py --gpus 1 --steps 20 --warmup 5 --full"),
         prof("headline_final", "--steps 1 --warmup 1 --no-single --no-energy"),
         prof("b1_llama_fp4_final", "--batch 1 --steps 1 --warmup 1 --no-energy --no-single --weights fp4"),
     ],
     # separate precision configurations of the headline workload (bf16 stays the headline), then the smoke test
     "r4_configs": [
-        ("cfg_fp4", 300, f"{PY} bench.py --weights fp4 --steps 3 --warmup 1 --no-single"),
-        ("cfg_fp4_kv8", 300, f"{PY} bench.py --weights fp4 --kv fp8 --steps 3 --warmup 1 --no-single"),
+        ("cfg_fp4", 300, f"{PY} bench.py --weights fp4 --steps 3 --warmup 1 --full --no-single"),
+        ("cfg_fp4_kv8", 300, f"{PY} bench.py --weights fp4 --kv fp8 --steps 3 --warmup 1 --full --no-single"),
         ("smoke", 300, f"{PY} -c 'import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")'"),
     ],
     # W4A16 vs W4A8 at mid widths (MXFP4 engines; runtime default: W4A8 above 64 rows)
@@ -218,11 +218,11 @@ SETS = {
                  f"--variants rule --dtypes fp4 --copies 0,8,1,0") for m in ("llama3.1:8b", "qwen2:1.5b")],
     "suite": [("gpu_suite", 1500, f"{PY} -u -m pytest tests -m gpu -x -q --timeout 600 --timeout-method thread")],
     # the driver's bench command
-    "bench": [("bench", 900, f"{PY} bench.py --gpus 1 --steps 20 --warmup 5")],
+    "bench": [("bench", 900, f"{PY} bench.py --gpus 1 --steps 20 --warmup 5 --full")],
     # round-5 evidence: the driver's bench command (7-model single stream, must fit the driver's 540 s), kernel stats
     # of the headline and of batch-1 fp4, the smoke test
     "r5_final": [
-        ("bench", 900, f"{PY} bench.py --gpus 1 --steps 20 --warmup 5"),
+        ("bench", 900, f"{PY} bench.py --gpus 1 --steps 20 --warmup 5 --full"),
         prof("headline_r5", "--steps 1 --warmup 1 --no-single --no-energy"),
         ("smoke", 300, f"{PY} -c 'import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")'"),
     ],
