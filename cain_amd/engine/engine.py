@@ -658,24 +658,49 @@ class DecodeEngine:
         return gens, 0, t1 - t0
 
 
-def sample_host(logits: torch.Tensor, history: List[int], o: Dict, rng) -> int:
-    """Host mirror of csrc/sample.hip (same pipeline; RNG differs)."""
-    lg = logits.clone()
-    if o["repeat_penalty"] != 1.0 and o["repeat_last_n"] > 0:
-        for t in set(history[-min(o["repeat_last_n"], 64):]):
-            v = lg[t]
-            lg[t] = v / o["repeat_penalty"] if v > 0 else v * o["repeat_penalty"]
+SAMPLE_TOPK_MAX = 256  # the kernels' top-k clamp (csrc/sample.hip SS_KMAX): top_k <= 0 or above it means this many
+SAMPLE_HIST = 64       # ids the repeat penalty can look back on (csrc/sample.hip HIST)
+
+
+def sample_host_candidates(logits: torch.Tensor, history: List[int], o: Dict):
+    """What the samplers of csrc/sample.hip draw from, computed on the host: ``(ids, probs, cut)`` -- the top-k
+    candidate ids after the repeat penalty (value descending, index ascending; the penalty in float32, each distinct
+    recent id inside the vocabulary once), their probabilities at the temperature (float64, normalised over the
+    candidates) and the number of leading candidates the top-p cut keeps (the smallest prefix whose cumulative
+    probability is >= top_p).  Greedy (temperature <= 0): the argmax alone, the lowest index on ties."""
+    lg = logits.detach().to(torch.float32).cpu().numpy().copy()
+    V = lg.shape[0]
+    rp = np.float32(o["repeat_penalty"])
+    if rp != np.float32(1.0) and o["repeat_last_n"] > 0:
+        n = min(int(o["repeat_last_n"]), SAMPLE_HIST, len(history))
+        for t in set(history[len(history) - n:]):
+            if 0 <= t < V:
+                v = lg[t]
+                lg[t] = v / rp if v > 0 else v * rp
     if o["temperature"] <= 0:
-        return int(torch.argmax(lg))
-    k = o["top_k"] if 0 < o["top_k"] <= 1024 else 1024
-    vals, idx = torch.topk(lg / o["temperature"], min(k, lg.numel()))
-    p = torch.softmax(vals.double(), 0)
-    if 0 < o["top_p"] < 1:
-        c = torch.cumsum(p, 0)
-        cut = int(torch.searchsorted(c, torch.tensor(o["top_p"], dtype=c.dtype))) + 1
-        p = p[:cut] / p[:cut].sum()
-        idx = idx[:cut]
-    return int(idx[int(rng.choice(len(p), p=p.numpy()))])
+        return np.array([int(np.argmax(lg))]), np.ones(1), 1
+    k = o["top_k"] if 0 < o["top_k"] <= SAMPLE_TOPK_MAX else SAMPLE_TOPK_MAX
+    k = min(k, V)
+    cand = np.flatnonzero(lg >= np.partition(lg, V - k)[V - k])  # every element >= the k-th largest (ties included)
+    ids = cand[np.lexsort((cand, -lg[cand].astype(np.float64)))][:k]  # value descending, index ascending
+    vals = lg[ids].astype(np.float64)
+    p = np.exp((vals - vals[0]) * np.float64(np.float32(1.0) / np.float32(o["temperature"])))
+    p /= p.sum()
+    cut = len(ids)
+    top_p = np.float64(np.float32(o["top_p"]))
+    if 0 < top_p < 1:
+        cut = min(int(np.searchsorted(np.cumsum(p), top_p, side="left")) + 1, len(ids))
+    return ids, p, cut
+
+
+def sample_host(logits: torch.Tensor, history: List[int], o: Dict, rng) -> int:
+    """Host mirror of csrc/sample.hip: the same candidates, order, probabilities and top-p cut
+    (sample_host_candidates); only the random stream differs (numpy's, the kernels hash seed and token index)."""
+    ids, p, cut = sample_host_candidates(logits, history, o)
+    if o["temperature"] <= 0:
+        return int(ids[0])
+    p = p[:cut] / p[:cut].sum()
+    return int(ids[int(rng.choice(cut, p=p))])
 
 
 class ContinuousBatch:
