@@ -113,11 +113,15 @@ def _stopped(toks: List[int], o: Dict) -> bool:
 
 # ============================================================== ctypes structs
 LAYER_FIELDS = ("wqkv", "bqkv", "wo", "wgu", "wdown", "sqkv", "so", "sgu", "sdown", "wqkv8", "wo8", "wgu8", "wdown8")
-WFMT = {"bf16": 0, "fp8": 1, "fp4": 2, "q4_0": 3, "q4_k": 4}  # runtime.hip WFMT_*
+LAYER_FORMATS = ("fqkv", "fo", "fgu", "fdown")  # per-matrix format ids of a GGUF plan, then the split V
+WFMT = {"bf16": 0, "fp8": 1, "fp4": 2, "q4_0": 3, "q4_k": 4, "q4_k_m": 4}  # runtime.hip WFMT_* (q4_k_m: Q4_K + MFMT)
+MFMT = {0: 3, 1: 4, 2: 5}  # models/q4.py format id -> runtime.hip WFMT_Q4_0 / WFMT_Q4_K / MFMT_Q6_K
+Q4_DTYPES = ("q4_0", "q4_k", "q4_k_m")
 
 
 class _CainLayer(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in LAYER_FIELDS]
+    _fields_ = ([(n, ctypes.c_void_p) for n in LAYER_FIELDS] + [(n, ctypes.c_int) for n in LAYER_FORMATS]
+                + [("wv", ctypes.c_void_p), ("sv", ctypes.c_void_p)])
 
 
 class _CainPlanDesc(ctypes.Structure):
@@ -130,7 +134,8 @@ class _CainPlanDesc(ctypes.Structure):
                                                  "part_o", "part_ml", "counters", "gemm_ws")]
                 + [("gemm_ws_bytes", ctypes.c_longlong), ("wfmt", ctypes.c_int), ("lm_head_scale", ctypes.c_void_p)]
                 + [("kv8", ctypes.c_int), ("lm_head8", ctypes.c_void_p), ("x8", ctypes.c_void_p),
-                   ("xs", ctypes.c_void_p), ("x8_ld", ctypes.c_int), ("q4_gain", ctypes.c_int)])
+                   ("xs", ctypes.c_void_p), ("x8_ld", ctypes.c_int), ("q4_gain", ctypes.c_int),
+                   ("flm_head", ctypes.c_int)])
 
 
 class _CainRows(ctypes.Structure):
@@ -179,14 +184,16 @@ def _load_ckpt(ckpt, cfg: ModelConfig, device, weight_dtype: str) -> ModelWeight
 
 
 def _attach_native(weights: ModelWeights, path, cfg: ModelConfig, weight_dtype: str, device) -> None:
-    """A GGUF checkpoint run on a GGUF block format (weight_dtype q4_0 / q4_k): keep its blocks as stored
-    (models/q4.py gguf_q4_native) for pack_for_engine, instead of re-quantising the decoded values."""
+    """A GGUF checkpoint run on a GGUF block format (weight_dtype q4_0 / q4_k / q4_k_m): keep its blocks as stored
+    (models/q4.py gguf_q4_native: the 4-bit format's and Q6_K's, whatever mix the file holds) for pack_for_engine,
+    instead of re-quantising the decoded values."""
     from ..models.gguf import GGUFFile, is_gguf
 
-    if weight_dtype in ("q4_0", "q4_k") and path and is_gguf(path):
-        from ..models.q4 import Q4_FORMATS, gguf_q4_native
+    if weight_dtype in Q4_DTYPES and path and is_gguf(path):
+        from ..models.q4 import gguf_q4_native
+        from ..models.weights import _q4_format
 
-        weights.native = gguf_q4_native(GGUFFile(path), cfg, Q4_FORMATS[weight_dtype], device=device)
+        weights.native = gguf_q4_native(GGUFFile(path), cfg, _q4_format(weight_dtype), device=device)
 
 
 class DecodeEngine:
@@ -215,6 +222,12 @@ class DecodeEngine:
         ``weight_dtype="q4_0" / "q4_k"``: llama.cpp's GGUF 4-bit blocks (Ollama's default builds) run natively
         (gemm_q4.hip: the block values as stored, scales applied per block; 16-row launches) up to 64 rows per
         forward; every GEMM K must be a multiple of 256.
+        ``weight_dtype="q4_k_m"``: Q4_K with the output head and the attn_v / ffn_down matrices of part of the
+        layers in Q6_K (gemm_q6.hip), the mix of Ollama's default Q4_K_M files (models/gguf.py q4_k_m_type) -- what
+        random-init and Hugging Face weights are laid out in.  A GGUF file loaded on ``q4_k`` or ``q4_k_m`` keeps
+        whatever mix of Q4_K and Q6_K tensors it stores (``weights.native["requantized"]`` lists the tensors of any
+        other type -- Q5_K, Q8_0, F16 ... -- and a Q6_K gate / up, which are re-quantised to Q4_K); a layer whose V
+        is Q6_K beside Q4_K q / k runs its QKV projection as two launches.
         ``kv_dtype="fp8"``: the KV cache holds e4m3 elements (half the attention bytes per decode step and half
         the cache memory; csrc/attention.hip KV8).
         ``cu_limit``: run every kernel on a stream whose hardware queue may use only that many CUs (a multiple of
@@ -225,7 +238,7 @@ class DecodeEngine:
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
         if weight_dtype == "fp4" and any(k % 128 for k in (self.cfg.d_model, self.cfg.q_dim, self.cfg.ffn)):
             raise ValueError(f"weight_dtype='fp4' needs d_model, q_dim and ffn to be multiples of 128 ({self.cfg.name})")
-        if weight_dtype in ("q4_0", "q4_k") and any(k % 256 for k in (self.cfg.d_model, self.cfg.q_dim, self.cfg.ffn)):
+        if weight_dtype in Q4_DTYPES and any(k % 256 for k in (self.cfg.d_model, self.cfg.q_dim, self.cfg.ffn)):
             raise ValueError(f"weight_dtype={weight_dtype!r} needs d_model, q_dim and ffn to be multiples of 256 "
                              f"({self.cfg.name})")
         if kv_dtype not in ("bf16", "fp8"):
@@ -242,7 +255,7 @@ class DecodeEngine:
         self.w4a8 = (weight_dtype == "fp4"
                      and all(k % 128 == 0 and k >= 512 for k in (self.cfg.d_model, self.cfg.q_dim, self.cfg.ffn)))
         row_cap = W8_MAX_ROWS if (weight_dtype == "fp4" and not self.w4a8) or (weight_dtype == "fp8" and not self.w8a8) \
-            or weight_dtype in ("q4_0", "q4_k") else MAX_ROWS
+            or weight_dtype in Q4_DTYPES else MAX_ROWS
         self.device = torch.device(device)
         if backend is None:
             backend = "hip" if self.device.type == "cuda" else "torch"
@@ -323,9 +336,13 @@ class DecodeEngine:
         self.sample_params = _ops.sample_params_tensor(
             [dict(temperature=0.0, top_p=1.0, repeat_penalty=1.0, top_k=1, repeat_last_n=0, eos_id=-1, seed=0)] * R,
             dev)
+        if self.weight_dtype in Q4_DTYPES:
+            self._check_gguf_shapes(packed)
         self._layers = (_CainLayer * L)()
         for i, lp in enumerate(packed["layers"]):
-            self._layers[i] = _CainLayer(*(_ptr(lp.get(k)) for k in LAYER_FIELDS))
+            self._layers[i] = _CainLayer(*(_ptr(lp.get(k)) for k in LAYER_FIELDS),
+                                         *(MFMT[lp[k]] if k in lp else 0 for k in LAYER_FORMATS),
+                                         _ptr(lp.get("wv")), _ptr(lp.get("sv")))
         self._packed = packed
         d = _CainPlanDesc()
         d.n_layers, d.d, d.H, d.Hkv, d.hd = L, cfg.d_model, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
@@ -361,6 +378,7 @@ class DecodeEngine:
         d.gemm_ws, d.gemm_ws_bytes = _ptr(self.gemm_ws), ws
         d.wfmt, d.lm_head_scale = WFMT[self.weight_dtype], _ptr(packed.get("lm_head_scale"))
         d.q4_gain = int(bool(packed.get("q4_gain")))  # GGUF blocks as stored: gains applied to the activations
+        d.flm_head = MFMT[packed["flm_head"]] if "flm_head" in packed else 0
         self._desc = d
         self._plans: Dict[int, int] = {}
         self._graphs: Dict[tuple, int] = {}
@@ -375,6 +393,26 @@ class DecodeEngine:
         else:
             self.cu_limit = 0
             self.stream = torch.cuda.Stream(device=dev)
+
+    def _check_gguf_shapes(self, packed) -> None:
+        """Refuse a model one of whose GEMMs the GGUF stream kernels cannot hold a single activation row of in LDS
+        (cain_gemm_q4_rows / cain_gemm_q6_rows == 0 for its K, epilogue and format): such a forward would fail at
+        its first launch of that shape."""
+        from ..ops import EPI_F32, EPI_GELU, EPI_QKV_ROPE, EPI_RESID, EPI_SILU
+
+        cfg = self.cfg
+        act = EPI_GELU if cfg.act == "gelu_tanh" else EPI_SILU
+        gemms = [("lm_head", packed.get("flm_head"), cfg.d_model, EPI_F32)]
+        for i, lp in enumerate(packed["layers"]):
+            gemms += [(f"layer {i} {n}", lp.get(f), k, e) for n, f, k, e in (
+                ("wqkv", "fqkv", cfg.d_model, EPI_QKV_ROPE), ("wv", "fv", cfg.d_model, EPI_QKV_ROPE),
+                ("wo", "fo", cfg.q_dim, EPI_RESID), ("wgu", "fgu", cfg.d_model, act),
+                ("wdown", "fdown", cfg.ffn, EPI_RESID)) if n in lp]
+        for name, f, k, epi in gemms:
+            rows = self.lib.cain_gemm_q6_rows(k, epi) if f == 2 else self.lib.cain_gemm_q4_rows(k, epi)
+            if int(rows) < 1:
+                raise ValueError(f"{cfg.name}: {name} (K = {k}, {'Q6_K' if f == 2 else 'Q4'}) does not fit the GGUF "
+                                 f"stream kernel's LDS copy of one activation row")
 
     def _wide_gemm_plans(self, R: int) -> list:
         """Split plans of the wide-batch GEMM (csrc/wgemm.hip) this engine runs, per projection shape at its

@@ -318,14 +318,37 @@ def quantize_q4_k(x: np.ndarray) -> np.ndarray:
     return q4k(torch.from_numpy(np.asarray(x, np.float32).reshape(-1, 256))).numpy().reshape(-1)
 
 
-_QUANT = {"Q8_0": quantize_q8_0, "Q4_0": quantize_q4_0, "Q4_K": quantize_q4_k}
+def quantize_q6_k(x: np.ndarray) -> np.ndarray:
+    """Q6_K blocks (models/q4.py's plain fit) of ``x`` (length a multiple of 256)."""
+    from .q4 import quantize_q6_k as q6k
+
+    return q6k(torch.from_numpy(np.asarray(x, np.float32).reshape(-1, 256))).numpy().reshape(-1)
+
+
+_QUANT = {"Q8_0": quantize_q8_0, "Q4_0": quantize_q4_0, "Q4_K": quantize_q4_k, "Q6_K": quantize_q6_k}
+
+
+def q4_k_m_type(name: str, n_layers: int, tied: bool = False) -> str:
+    """The type llama.cpp's Q4_K_M mix gives the 2-D tensor ``name`` of an ``n_layers`` model: ``output.weight``
+    (``token_embd.weight`` when the head is ``tied`` to it) is Q6_K, ``attn_v`` and ``ffn_down`` are Q6_K in layers
+    i < n / 8, i >= 7 n / 8 and (i - n / 8) % 3 == 2 (integer n / 8), everything else is Q4_K.  The rule is quoted
+    from memory of llama.cpp's quantiser: no copy of it can be consulted here, so it is unverified -- a real file
+    loads by the types it stores, whatever they are (``models/q4.py gguf_q4_native``)."""
+    if name == "output.weight" or (tied and name == "token_embd.weight"):
+        return "Q6_K"
+    m = re.fullmatch(r"blk\.(\d+)\.(attn_v|ffn_down)\.weight", name)
+    if m:
+        i, e = int(m.group(1)), n_layers // 8
+        if i < e or i >= 7 * n_layers // 8 or (i - e) % 3 == 2:
+            return "Q6_K"
+    return "Q4_K"
 
 
 # ---------------------------------------------------------------------------------------------------- writer
 def write_gguf(path: Union[str, os.PathLike], metadata: Dict[str, Any], tensors: Dict[str, Tuple[np.ndarray, str]],
                alignment: int = 32) -> None:
     """A GGUF v3 file: ``metadata`` (str / int / float / bool / list values) and ``tensors`` name -> (array in torch
-    order, type name among F32 / F16 / BF16 / Q8_0 / Q4_0).  Used by the tests and by ``export_gguf``."""
+    order, type name among F32 / F16 / BF16 / Q8_0 / Q4_0 / Q4_K / Q6_K).  Used by the tests and by ``export_gguf``."""
     def s(x: str) -> bytes:
         b = x.encode("utf-8")
         return struct.pack("<Q", len(b)) + b
@@ -587,11 +610,13 @@ def gguf_tokenizer_fields(tokenizer_json: Dict[str, Any], bos_id: Optional[int] 
     return out
 
 
-def export_gguf(mw: ModelWeights, path: Union[str, os.PathLike], arch: str, tensor_type: str = "F16",
+def export_gguf(mw: ModelWeights, path: Union[str, os.PathLike], arch: str, tensor_type="F16",
                 tokenizer_fields: Optional[Dict[str, Any]] = None, context_length: Optional[int] = None) -> None:
     """Write ``mw`` as a GGUF file of ``arch`` with llama.cpp's conventions (the inverse of ``load_gguf``): q / k
     rows permuted for ``llama``, Gemma gains as 1 + w, Phi-3's fused qkv / gate-up, Llama-3 scaling as a
-    ``rope_freqs`` tensor.  2-D weights in ``tensor_type`` (F32 / F16 / BF16 / Q8_0 / Q4_0), norms in F32."""
+    ``rope_freqs`` tensor.  2-D weights in ``tensor_type`` (F32 / F16 / BF16 / Q8_0 / Q4_0 / Q4_K / Q6_K), norms in
+    F32.  ``tensor_type`` may also choose per tensor: ``"Q4_K_M"`` (llama.cpp's mix as ``q4_k_m_type`` has it: an
+    unverified rule) or a callable tensor name -> type name."""
     from .config import rope_inv_freq
 
     cfg = mw.cfg
@@ -610,8 +635,15 @@ def export_gguf(mw: ModelWeights, path: Union[str, os.PathLike], arch: str, tens
     md.update(tokenizer_fields or {})
     T: Dict[str, Tuple[np.ndarray, str]] = {}
 
+    def type_of(name: str) -> str:
+        if callable(tensor_type):
+            return tensor_type(name)
+        if tensor_type == "Q4_K_M":
+            return q4_k_m_type(name, cfg.n_layers, tied=cfg.tie_embeddings)
+        return tensor_type
+
     def put(name, t, typ=None):
-        T[name] = (t.detach().float().cpu().numpy(), typ or (tensor_type if t.dim() == 2 else "F32"))
+        T[name] = (t.detach().float().cpu().numpy(), typ or (type_of(name) if t.dim() == 2 else "F32"))
 
     def gain(t):
         return t.float() + 1.0 if arch == "gemma" else t

@@ -16,6 +16,11 @@ them and only their layout changes:
 Q4_K's quantiser is a plain min/max fit (per 32: scale (max - min) / 15, min -min; per 256: d, dmin = the largest
 / 63), not llama.cpp's iterative ``make_qkx2_quants`` search: the kernel runs whatever valid blocks a file holds,
 and random weights only need valid blocks of the right layout.
+
+Q6_K (format id ``Q6_K`` = 2; ``ops/csrc/gemm_q6.hip``) is the type a Q4_K_M file keeps its output head and part of
+its ``attn_v`` / ``ffn_down`` tensors in: ``q6_fields`` / ``pack_q6`` / ``quantize_q6_k`` are its members of the same
+three steps, ``gguf_q4_native`` keeps such tensors as stored beside the plan's 4-bit format, and ``q4_k_m_formats``
+is the per-matrix mix ``weight_dtype="q4_k_m"`` lays random or Hugging Face weights out in.
 """
 from __future__ import annotations
 
@@ -26,9 +31,10 @@ import torch
 from .gguf import _k_scale_min, dequantize
 
 Q4_FORMATS = {"q4_0": 0, "q4_k": 1}  # gemm_q4.hip Q4F_*
-_BLOCK_BYTES = {0: 18, 1: 144}
-_BLOCK_ELEMS = {0: 32, 1: 256}
-GGML_TYPE = {0: 2, 1: 12}  # ggml type ids of Q4_0 / Q4_K
+Q6_K = 2                              # gemm_q6.hip Q6F_K
+_BLOCK_BYTES = {0: 18, 1: 144, 2: 210}
+_BLOCK_ELEMS = {0: 32, 1: 256, 2: 256}
+GGML_TYPE = {0: 2, 1: 12, 2: 14}  # ggml type ids of Q4_0 / Q4_K / Q6_K
 
 
 def _fp16_bytes(x: torch.Tensor) -> torch.Tensor:
@@ -76,8 +82,35 @@ def quantize_q4_k(w: torch.Tensor) -> torch.Tensor:
     return torch.cat([_fp16_bytes(d), _fp16_bytes(dmin), scales, qs], -1).contiguous()
 
 
+def quantize_q6_k(w: torch.Tensor) -> torch.Tensor:
+    """Q6_K blocks of ``w`` [N, K] (K % 256 == 0) as uint8 [N, K / 256, 210]: [ql 128: low nibbles][qh 64: high bit
+    pairs][16 int8 group scales][d fp16], w = d sc (q - 32), q in 0..63, one sc per 16 elements.  A plain fit, not
+    llama.cpp's ``make_qx_quants`` error search: per group the scale is (the signed value of largest magnitude) /
+    -32, the sign ggml picks so that this value lands on the code 0 exactly (so about half the scales are
+    negative); per super-block d = the largest |scale| / 127 and sc = round(scale / d); the codes are then taken
+    with the scale the block really stores, d sc."""
+    n, k = w.shape
+    x = w.float().reshape(n, k // 256, 16, 16)
+    idx = x.abs().argmax(-1, keepdim=True)
+    scale = torch.gather(x, -1, idx)[..., 0] / -32.0              # [n, sb, 16]
+    d = scale.abs().amax(-1) / 127.0                              # [n, sb]
+    d16 = d.to(torch.float16).float()
+    safe = lambda v: torch.where(v != 0, v, torch.ones_like(v))  # noqa: E731
+    sc = torch.where(d16[..., None] > 0, torch.round(scale / safe(d16)[..., None]), torch.zeros_like(scale))
+    sc = sc.clamp(-128, 127)
+    s = d16[..., None] * sc                                       # the scale the decoder applies
+    q = torch.where(s[..., None] != 0, torch.round(x / safe(s)[..., None]), torch.zeros_like(x))
+    q = (q.clamp(-32, 31) + 32).to(torch.uint8).reshape(n, k // 256, 2, 4, 32)  # [half, quarter, l]: 128 h + 32 j + l
+    lo, hi = q & 15, q >> 4
+    ql = torch.cat([lo[..., 0, :] | (lo[..., 2, :] << 4), lo[..., 1, :] | (lo[..., 3, :] << 4)], -1)  # [n, sb, 2, 64]
+    qh = hi[..., 0, :] | (hi[..., 1, :] << 2) | (hi[..., 2, :] << 4) | (hi[..., 3, :] << 6)            # [n, sb, 2, 32]
+    return torch.cat([ql.reshape(n, k // 256, 128), qh.reshape(n, k // 256, 64),
+                      sc.to(torch.int8).view(torch.uint8), _fp16_bytes(d)], -1).contiguous()
+
+
 def quantize_q4(w: torch.Tensor, fmt: int) -> torch.Tensor:
-    return quantize_q4_0(w) if fmt == 0 else quantize_q4_k(w)
+    """``w`` [N, K] as ggml blocks of format id ``fmt`` (0 Q4_0, 1 Q4_K, 2 Q6_K)."""
+    return quantize_q4_0(w) if fmt == 0 else quantize_q4_k(w) if fmt == 1 else quantize_q6_k(w)
 
 
 def dequantize_q4(blocks: torch.Tensor, fmt: int, n: int, k: int) -> torch.Tensor:
@@ -102,6 +135,45 @@ def q4_fields(blocks: torch.Tensor, fmt: int, n: int, k: int) -> Dict[str, torch
             "m": mn.to(torch.uint8).reshape(n, k // 32),
             "d": b[..., 0:2].contiguous().view(torch.float16)[..., 0],
             "dmin": b[..., 2:4].contiguous().view(torch.float16)[..., 0]}
+
+
+def q6_fields(blocks: torch.Tensor, n: int, k: int) -> Dict[str, torch.Tensor]:
+    """ggml Q6_K block bytes (any shape holding N K / 256 blocks, rows in order) -> ``codes`` uint8 [N, K] in 0..63,
+    ``sc`` int8 [N, K / 16] and ``d`` fp16 [N, K / 256].  Bit-exact: no value is recomputed."""
+    b = blocks.reshape(n, k // 256, 210)
+    ql = b[..., 0:128].reshape(n, k // 256, 2, 64)
+    qh = b[..., 128:192].reshape(n, k // 256, 2, 32)
+    q = torch.stack([(ql[..., :32] & 15) | ((qh & 3) << 4), (ql[..., 32:] & 15) | (((qh >> 2) & 3) << 4),
+                     (ql[..., :32] >> 4) | (((qh >> 4) & 3) << 4), (ql[..., 32:] >> 4) | ((qh >> 6) << 4)], 3)
+    return {"codes": q.reshape(n, k).contiguous(),       # [sb, half, quarter, 32] = element order
+            "sc": b[..., 192:208].contiguous().view(torch.int8).reshape(n, k // 16),
+            "d": b[..., 208:210].contiguous().view(torch.float16)[..., 0]}
+
+
+def pack_q6(fields: Dict[str, torch.Tensor], gain: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``q6_fields`` -> (codes uint8 [N / 16, K / 128, 1536], scale buffer uint8) in gemm_q6.hip's layout: per (tile,
+    128-k quad) [64 lanes x 16 bytes of low nibbles][64 lanes x 8 bytes of high bit pairs], lane l = 16 g + r holding
+    row 16 t + r; group s of the quad (k = 128 p + 16 s + 4 g + j) sits in byte j of low dword s >> 1 (nibble s & 1)
+    and of high dword s >> 2 (bits 2 (s & 3)).  The scale buffer is [per (t, p, r): 8 int8 group scales][per (t,
+    super-block, r): d as fp32][gain]: 6 + 0.5 + 0.125 bits per weight."""
+    codes = fields["codes"]
+    n, k = codes.shape
+    if n % 16 or k % 256:
+        raise ValueError(f"pack_q6 needs N % 16 == 0 and K % 256 == 0, got {tuple(codes.shape)}")
+    nt, kq = n // 16, k // 128
+    lo = (codes & 15).reshape(nt, 16, kq, 4, 2, 4, 4)           # [t, r, p, dword, nibble, g, j]
+    lo = lo.permute(0, 2, 5, 1, 3, 6, 4)                        # [t, p, g, r, dword, j, nibble]
+    lo = (lo[..., 0] | (lo[..., 1] << 4)).reshape(nt, kq, 1024)
+    hi = (codes >> 4).reshape(nt, 16, kq, 2, 4, 4, 4)           # [t, r, p, dword, pair, g, j]
+    hi = hi.permute(0, 2, 5, 1, 3, 6, 4)                        # [t, p, g, r, dword, j, pair]
+    hi = (hi[..., 0] | (hi[..., 1] << 2) | (hi[..., 2] << 4) | (hi[..., 3] << 6)).reshape(nt, kq, 512)
+    wq = torch.cat([lo, hi], -1).contiguous()
+    sc = fields["sc"].reshape(nt, 16, kq, 8).permute(0, 2, 1, 3).contiguous().view(torch.uint8).reshape(-1)
+    d = fields["d"].float().reshape(nt, 16, k // 256).permute(0, 2, 1).contiguous().view(torch.uint8).reshape(-1)
+    parts = [sc, d]
+    if gain is not None:
+        parts.append(gain.float().contiguous().view(torch.uint8).reshape(-1))
+    return wq, torch.cat(parts).contiguous()
 
 
 def pack_q4(fields: Dict[str, torch.Tensor], fmt: int, gain: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor,
@@ -134,8 +206,7 @@ def pack_q4(fields: Dict[str, torch.Tensor], fmt: int, gain: Optional[torch.Tens
 
 def quant_pack_q4(w: torch.Tensor, fmt: int, gain: Optional[torch.Tensor] = None):
     """Quantise ``w`` [N, K] to ggml blocks and pack them: (codes, scale buffer)."""
-    n, k = w.shape
-    return pack_q4(q4_fields(quantize_q4(w, fmt), fmt, n, k), fmt, gain)
+    return pack_native(quantize_q4(w, fmt), fmt, gain)
 
 
 def q4_roundtrip(w: torch.Tensor, fmt: int) -> torch.Tensor:
@@ -144,56 +215,95 @@ def q4_roundtrip(w: torch.Tensor, fmt: int) -> torch.Tensor:
     return dequantize_q4(quantize_q4(w, fmt), fmt, n, k).to(w.dtype)
 
 
+
+
+def q4_k_m_formats(cfg) -> Dict[str, object]:
+    """The per-matrix format ids of ``weight_dtype="q4_k_m"``: llama.cpp's Q4_K_M mix (``gguf.q4_k_m_type``) over
+    this engine's matrices -- {"layers": [{wqkv, wv, wo, wgu, w_down}], "lm_head"}; ``wv`` differs from ``wqkv`` in
+    the layers whose V rows are Q6_K (a launch of their own, runtime.hip)."""
+    from .gguf import q4_k_m_type
+
+    ids = {"Q4_K": 1, "Q6_K": Q6_K}
+    layers = []
+    for i in range(cfg.n_layers):
+        t = lambda x: ids[q4_k_m_type(f"blk.{i}.{x}.weight", cfg.n_layers)]  # noqa: E731
+        layers.append({"wqkv": t("attn_q"), "wv": t("attn_v"), "wo": t("attn_output"), "wgu": t("ffn_gate"),
+                       "w_down": t("ffn_down")})
+    return {"layers": layers, "lm_head": ids[q4_k_m_type("output.weight", cfg.n_layers)]}
+
+
 def gguf_q4_native(g, cfg, fmt: int, device="cpu") -> Dict[str, object]:
-    """A GGUF file's GEMM weights as ggml blocks of ``fmt`` (uint8 [N, K / elems, bytes]) in the engine's natural
-    row order -- the same row operations as ``gguf.load_gguf_weights`` (Llama q / k un-permuted, q / k / v
-    concatenated, Phi-3's fused gate/up split), applied to whole rows of blocks, so no value changes.  Tensors the
-    file stores in another type (a Q4_K_M file's Q6_K tensors, an F16 output head) are quantised to ``fmt`` from
-    their decoded values and listed under ``requantized``.  Result: {"fmt", "layers": [{wqkv, wo, w_gate, w_up,
-    w_down}], "lm_head", "requantized"}, attached to ``ModelWeights.native`` for ``pack_for_engine``."""
+    """A GGUF file's GEMM weights as ggml blocks (uint8 [N, K / elems, bytes]) in the engine's natural row order --
+    the same row operations as ``gguf.load_gguf_weights`` (Llama q / k un-permuted, q / k / v concatenated, Phi-3's
+    fused gate/up split), applied to whole rows of blocks, so no value changes.  A tensor stored as ``fmt`` (the
+    plan's 4-bit format) or as Q6_K (a Q4_K_M file's output head and part of its attn_v / ffn_down) stays as stored;
+    each matrix's format id is recorded under ``fmts``.  The fused QKV takes one format: where V's differs from q /
+    k's (Q4_K_M), V is returned on its own under ``wv`` and ``wqkv`` holds the q and k rows only.  What is
+    quantised to ``fmt`` from its decoded values instead, and listed under ``requantized``: tensors of any other
+    type (Q5_K, Q8_0, F16 ...), q and k when their types differ from each other, and a Q6_K gate / up (gemm_q6.hip
+    has no gate/up activation epilogue).  Result: {"fmt", "layers": [{wqkv, [wv,] wo, w_gate, w_up, w_down, fmts}],
+    "lm_head", "lm_head_fmt", "requantized"}, attached to ``ModelWeights.native`` for ``pack_for_engine``."""
     import numpy as np
 
     from .gguf import unpermute_qk
 
     arch = g.metadata["general.architecture"]
-    bb, be = _BLOCK_BYTES[fmt], _BLOCK_ELEMS[fmt]
     requant = []
 
-    def blocks(name: str) -> torch.Tensor:
+    def stored(name: str) -> Optional[int]:  # the format id the tensor can run as stored in
+        return next((f for f in (fmt, Q6_K) if g.tensors[name].type == GGML_TYPE[f]), None)
+
+    def blocks(name: str, q6: bool = True) -> Tuple[torch.Tensor, int]:
         t = g.tensors[name]
         n, k = t.shape
-        if t.type == GGML_TYPE[fmt]:
-            return torch.from_numpy(np.array(g.raw(name))).to(device).reshape(n, k // be, bb)
+        f = stored(name)
+        if f is not None and (q6 or f == fmt):
+            return torch.from_numpy(np.array(g.raw(name))).to(device).reshape(n, k // _BLOCK_ELEMS[f],
+                                                                              _BLOCK_BYTES[f]), f
         requant.append(f"{name} ({t.type_name})")
-        return quantize_q4(g.tensor(name, device=device, dtype=torch.float32), fmt)
+        return quantize_q4(g.tensor(name, device=device, dtype=torch.float32), fmt), fmt
 
     f = cfg.ffn
     layers = []
     for i in range(cfg.n_layers):
         p = f"blk.{i}."
+        lw: Dict[str, object] = {}
+        fm: Dict[str, int] = {}
         if g.has(p + "attn_qkv.weight"):
-            qkv = blocks(p + "attn_qkv.weight")
+            qkv, fm["wqkv"] = blocks(p + "attn_qkv.weight")
         else:
-            q, kk = blocks(p + "attn_q.weight"), blocks(p + "attn_k.weight")
+            v, fv = blocks(p + "attn_v.weight")
+            # q / k stay Q6_K only beside a Q6_K V: a separate V launch is always gemm_q6's (it takes the tile offset)
+            same = stored(p + "attn_q.weight") == stored(p + "attn_k.weight") and fv == Q6_K
+            (q, fq), (kk, _) = blocks(p + "attn_q.weight", same), blocks(p + "attn_k.weight", same)
             if arch == "llama":
                 q, kk = unpermute_qk(q, cfg.n_heads), unpermute_qk(kk, cfg.n_kv_heads)
-            qkv = torch.cat([q, kk, blocks(p + "attn_v.weight")], 0)
+            fm["wqkv"] = fq
+            if fv == fq:
+                qkv = torch.cat([q, kk, v], 0)
+            else:
+                qkv, lw["wv"], fm["wv"] = torch.cat([q, kk], 0), v.contiguous(), fv
         if g.has(p + "ffn_gate.weight"):
-            gate, up = blocks(p + "ffn_gate.weight"), blocks(p + "ffn_up.weight")
+            (gate, _), (up, _) = blocks(p + "ffn_gate.weight", False), blocks(p + "ffn_up.weight", False)
         else:  # phi3: ffn_up = [gate; up]
-            gu = blocks(p + "ffn_up.weight")
+            gu, _ = blocks(p + "ffn_up.weight", False)
             gate, up = gu[:f].contiguous(), gu[f:].contiguous()
-        layers.append({"wqkv": qkv.contiguous(), "wo": blocks(p + "attn_output.weight"), "w_gate": gate,
-                       "w_up": up, "w_down": blocks(p + "ffn_down.weight")})
-    lm = blocks("output.weight") if g.has("output.weight") else blocks("token_embd.weight")
-    return {"fmt": fmt, "layers": layers, "lm_head": lm, "requantized": requant}
+        fm["wgu"] = fmt
+        lw["wo"], fm["wo"] = blocks(p + "attn_output.weight")
+        lw["w_down"], fm["w_down"] = blocks(p + "ffn_down.weight")
+        lw.update({"wqkv": qkv.contiguous(), "w_gate": gate, "w_up": up, "fmts": fm})
+        layers.append(lw)
+    lm, flm = blocks("output.weight") if g.has("output.weight") else blocks("token_embd.weight")
+    return {"fmt": fmt, "layers": layers, "lm_head": lm, "lm_head_fmt": flm, "requantized": requant}
 
 
 def pack_native(blocks: torch.Tensor, fmt: int, gain: Optional[torch.Tensor] = None,
                 rows: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Pack ggml blocks [N, K / elems, bytes] (rows reordered by ``rows`` first) for the kernel, the RMSNorm gain
-    appended unfolded (a file's values stay exact)."""
+    """Pack ggml blocks [N, K / elems, bytes] of format id ``fmt`` (rows reordered by ``rows`` first) for their
+    kernel (``pack_q4`` / ``pack_q6``), the RMSNorm gain appended unfolded (a file's values stay exact)."""
     n = blocks.shape[0]
     k = blocks.shape[1] * _BLOCK_ELEMS[fmt]
-    b = blocks if rows is None else blocks[rows]
-    return pack_q4(q4_fields(b.contiguous(), fmt, n, k), fmt, gain)
+    b = (blocks if rows is None else blocks[rows]).contiguous()
+    if fmt == Q6_K:
+        return pack_q6(q6_fields(b, n, k), gain)
+    return pack_q4(q4_fields(b, fmt, n, k), fmt, gain)

@@ -227,8 +227,8 @@ class ModelWeights:
     lm_head: torch.Tensor               # [V, d] (aliases embed when tied)
     layers: List[LayerWeights]
     packed: Dict[str, object] = field(default_factory=dict)
-    # weights kept in a file's quantised form (models/q4.py gguf_q4_native: GGUF Q4_0 / Q4_K blocks), packed as
-    # stored by pack_for_engine when the engine's weight_dtype is that format
+    # weights kept in a file's quantised form (models/q4.py gguf_q4_native: GGUF Q4_0 / Q4_K blocks, Q6_K tensors
+    # beside them), packed as stored by pack_for_engine when the engine's weight_dtype is that format
     native: Dict[str, object] = field(default_factory=dict)
 
     @property
@@ -314,14 +314,43 @@ def mxfp4_roundtrip_weights(mw: ModelWeights) -> ModelWeights:
 
 
 def q4_roundtrip_weights(mw: ModelWeights, weight_dtype: str) -> ModelWeights:
-    """The torch oracle of a ``weight_dtype="q4_0" / "q4_k"`` engine: the ggml blocks of W diag(g), dequantised by
-    gguf.py's decoders (``_roundtrip``; models/q4.py)."""
-    from .q4 import Q4_FORMATS, q4_roundtrip
+    """The torch oracle of a ``weight_dtype="q4_0" / "q4_k" / "q4_k_m"`` engine: the ggml blocks of W diag(g),
+    dequantised by gguf.py's decoders (``_roundtrip``; models/q4.py)."""
+    from .q4 import q4_roundtrip
 
-    fmt = Q4_FORMATS[weight_dtype]
+    fmt = _q4_format(weight_dtype)
     if mw.native.get("fmt") == fmt:
         return mw  # a GGUF file's blocks run as stored: the loaded (decoded) weights are the values, gains separate
-    return _roundtrip(mw, lambda w: q4_roundtrip(w, fmt))
+    if weight_dtype != "q4_k_m":
+        return _roundtrip(mw, lambda w: q4_roundtrip(w, fmt))
+    # each matrix through its own format of the Q4_K_M mix; V's rows apart from q / k's where their formats differ
+    from .q4 import q4_k_m_formats
+
+    cfg = mw.cfg
+    fm = q4_k_m_formats(cfg)
+    nqk = cfg.q_dim + cfg.kv_dim
+    layers = []
+    for lw, f in zip(mw.layers, fm["layers"]):
+        ga, gm = effective_gain(cfg, lw.attn_norm), effective_gain(cfg, lw.mlp_norm)
+        wqkv = fold_gain(lw.wqkv, ga)
+        wqkv = torch.cat([q4_roundtrip(wqkv[:nqk], f["wqkv"]), q4_roundtrip(wqkv[nqk:], f["wv"])], 0)
+        layers.append(LayerWeights(attn_norm=_unit_gain(cfg, lw.attn_norm), wqkv=wqkv, bqkv=lw.bqkv,
+                                   wo=q4_roundtrip(lw.wo, f["wo"]), mlp_norm=_unit_gain(cfg, lw.mlp_norm),
+                                   w_gate=q4_roundtrip(fold_gain(lw.w_gate, gm), f["wgu"]),
+                                   w_up=q4_roundtrip(fold_gain(lw.w_up, gm), f["wgu"]),
+                                   w_down=q4_roundtrip(lw.w_down, f["w_down"])))
+    lm = q4_roundtrip(fold_gain(mw.lm_head, effective_gain(cfg, mw.final_norm)), fm["lm_head"])
+    return ModelWeights(cfg, mw.embed, _unit_gain(cfg, mw.final_norm), lm, layers)
+
+
+Q4_DTYPES = ("q4_0", "q4_k", "q4_k_m")
+
+
+def _q4_format(weight_dtype: str) -> int:
+    """The plan's 4-bit block format id (models/q4.py) of a GGUF weight_dtype: q4_k_m is Q4_K with Q6_K matrices."""
+    from .q4 import Q4_FORMATS
+
+    return Q4_FORMATS["q4_k" if weight_dtype == "q4_k_m" else weight_dtype]
 
 
 def roundtrip_weights(mw: ModelWeights, weight_dtype: str) -> ModelWeights:
@@ -330,13 +359,15 @@ def roundtrip_weights(mw: ModelWeights, weight_dtype: str) -> ModelWeights:
         return fp8_roundtrip_weights(mw)
     if weight_dtype == "fp4":
         return mxfp4_roundtrip_weights(mw)
-    if weight_dtype in ("q4_0", "q4_k"):
+    if weight_dtype in Q4_DTYPES:
         return q4_roundtrip_weights(mw, weight_dtype)
     return mw
 
 
-# q4_0 / q4_k: llama.cpp's GGUF block formats (models/q4.py, ops/csrc/gemm_q4.hip), Ollama's default builds
-WEIGHT_DTYPES = ("bf16", "fp8", "fp4", "q4_0", "q4_k")
+# q4_0 / q4_k: llama.cpp's GGUF block formats (models/q4.py, ops/csrc/gemm_q4.hip), Ollama's default builds;
+# q4_k_m: Q4_K with the output head and part of the V / down projections in Q6_K (ops/csrc/gemm_q6.hip), the mix
+# Ollama's default Q4_K_M files store
+WEIGHT_DTYPES = ("bf16", "fp8", "fp4", "q4_0", "q4_k", "q4_k_m")
 
 
 def pack_for_engine(mw: ModelWeights, free_natural: bool = False, weight_dtype: str = "bf16",
@@ -349,19 +380,23 @@ def pack_for_engine(mw: ModelWeights, free_natural: bool = False, weight_dtype: 
     ``w8a8`` the same e4m3 bytes are also stored in the W8A8 wide kernel's packing under ``<name>8``.
     ``weight_dtype="fp4"``: MXFP4 (``quantize_mxfp4``), the ``pack_mxfp4`` bytes under ``<name>`` and the e8m0
     scale bytes under ``s<name>``.  ``weight_dtype="q4_0" / "q4_k"``: ggml blocks of the gain-folded weights
-    (models/q4.py), the ``pack_q4`` codes under ``<name>`` and its scale buffer under ``s<name>``."""
+    (models/q4.py), the ``pack_q4`` codes under ``<name>`` and its scale buffer under ``s<name>``.
+    ``weight_dtype="q4_k_m"``: the same with each matrix in its format of the Q4_K_M mix.  Every GGUF plan records
+    the format id of each matrix under ``f<name>`` (``flm_head``; 0: the plan's own) and, where V's format differs
+    from q / k's, packs the V rows on their own under ``wv`` / ``sv`` (``wqkv`` then holds the q and k rows)."""
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
     cfg = mw.cfg
     fp8 = weight_dtype == "fp8"
     fp4 = weight_dtype == "fp4"
-    q4 = weight_dtype in ("q4_0", "q4_k")
+    q4 = weight_dtype in Q4_DTYPES
     perm = qkv_row_permutation(cfg).to(mw.device)
+    nqk = cfg.q_dim + cfg.kv_dim  # the q and k rows of the fused QKV: V is the trailing, unpermuted block
 
     native = None
     if q4:
-        from .q4 import Q4_FORMATS, pack_native
-        if mw.native.get("fmt") == Q4_FORMATS[weight_dtype]:
+        from .q4 import pack_native
+        if mw.native.get("fmt") == _q4_format(weight_dtype):
             native = mw.native
     if native is not None:
         # a GGUF file's blocks as stored: row operations only (QKV RoPE order, gate/up interleave), the norm gains
@@ -371,24 +406,37 @@ def pack_for_engine(mw: ModelWeights, free_natural: bool = False, weight_dtype: 
         for lw, nl in zip(mw.layers, native["layers"]):
             ga = effective_gain(cfg, lw.attn_norm).float()
             gm = effective_gain(cfg, lw.mlp_norm).float()
+            fm = nl.get("fmts", {})
             lp: Dict[str, object] = {"bqkv": None if lw.bqkv is None else lw.bqkv.float()[perm].contiguous()}
-            lp["wqkv"], lp["sqkv"] = pack_native(nl["wqkv"], fmt, ga, rows=perm)
-            lp["wo"], lp["so"] = pack_native(nl["wo"], fmt)
+            split = "wv" in nl
+            lp["wqkv"], lp["sqkv"] = pack_native(nl["wqkv"], fm.get("wqkv", fmt), ga, rows=perm[:nqk] if split else perm)
+            if split:
+                lp["wv"], lp["sv"], lp["fv"] = *pack_native(nl["wv"], fm["wv"], ga), fm["wv"]
+            lp["wo"], lp["so"] = pack_native(nl["wo"], fm.get("wo", fmt))
             g_, u_ = nl["w_gate"], nl["w_up"]
             gu = interleave_tiles(g_.reshape(g_.shape[0], -1), u_.reshape(u_.shape[0], -1), tile=8)
-            lp["wgu"], lp["sgu"] = pack_native(gu.reshape(-1, *g_.shape[1:]), fmt, gm)
-            lp["wdown"], lp["sdown"] = pack_native(nl["w_down"], fmt)
+            lp["wgu"], lp["sgu"] = pack_native(gu.reshape(-1, *g_.shape[1:]), fm.get("wgu", fmt), gm)
+            lp["wdown"], lp["sdown"] = pack_native(nl["w_down"], fm.get("w_down", fmt))
+            lp.update(fqkv=fm.get("wqkv", fmt), fo=fm.get("wo", fmt), fgu=fm.get("wgu", fmt),
+                      fdown=fm.get("w_down", fmt))
             layers.append(lp)
         packed = {"layers": layers, "weight_dtype": weight_dtype, "q4_gain": True}
-        packed["lm_head"], packed["lm_head_scale"] = pack_native(native["lm_head"], fmt,
+        packed["flm_head"] = native.get("lm_head_fmt", fmt)
+        packed["lm_head"], packed["lm_head_scale"] = pack_native(native["lm_head"], packed["flm_head"],
                                                                  effective_gain(cfg, mw.final_norm).float())
         mw.packed = packed
         return packed
 
-    def put(dst: Dict[str, object], name: str, w: torch.Tensor) -> None:
+    mix = None
+    if weight_dtype == "q4_k_m":
+        from .q4 import q4_k_m_formats
+        mix = q4_k_m_formats(cfg)
+
+    def put(dst: Dict[str, object], name: str, w: torch.Tensor, f: Optional[int] = None) -> None:
         if q4:
-            from .q4 import Q4_FORMATS, quant_pack_q4
-            dst[name], dst["s" + name[1:]] = quant_pack_q4(w, Q4_FORMATS[weight_dtype])
+            from .q4 import quant_pack_q4
+            f = _q4_format(weight_dtype) if f is None else f
+            dst[name], dst["s" + name[1:]], dst["f" + name[1:]] = *quant_pack_q4(w, f), f
         elif fp4:
             dst[name], dst["s" + name[1:]] = pack_mxfp4(*quantize_mxfp4(w))
         elif fp8:
@@ -400,21 +448,27 @@ def pack_for_engine(mw: ModelWeights, free_natural: bool = False, weight_dtype: 
             dst[name] = pack_mfma_a(w)
 
     layers = []
-    for lw in mw.layers:
+    for i, lw in enumerate(mw.layers):
         ga = effective_gain(cfg, lw.attn_norm)
         gm = effective_gain(cfg, lw.mlp_norm)
         lp: Dict[str, object] = {"bqkv": None if lw.bqkv is None else lw.bqkv.float()[perm].contiguous()}
-        put(lp, "wqkv", fold_gain(lw.wqkv[perm], ga))
-        put(lp, "wo", lw.wo)
+        fm = mix["layers"][i] if mix else {}
+        wqkv = fold_gain(lw.wqkv[perm], ga)
+        if mix and fm["wv"] != fm["wqkv"]:
+            put(lp, "wqkv", wqkv[:nqk], fm["wqkv"])
+            put(lp, "wv", wqkv[nqk:], fm["wv"])
+        else:
+            put(lp, "wqkv", wqkv, fm.get("wqkv"))
+        put(lp, "wo", lw.wo, fm.get("wo"))
         wgu = interleave_tiles(fold_gain(lw.w_gate, gm), fold_gain(lw.w_up, gm), tile=8)
-        put(lp, "wgu", wgu)
-        put(lp, "wdown", lw.w_down)
+        put(lp, "wgu", wgu, fm.get("wgu"))
+        put(lp, "wdown", lw.w_down, fm.get("w_down"))
         layers.append(lp)
         if free_natural:
             lw.wqkv = lw.wo = lw.w_gate = lw.w_up = lw.w_down = None
     packed: Dict[str, object] = {"layers": layers, "weight_dtype": weight_dtype}
     lm = fold_gain(mw.lm_head, effective_gain(cfg, mw.final_norm))
-    put(packed, "wlm_head", lm)
+    put(packed, "wlm_head", lm, mix["lm_head"] if mix else None)
     del lm
     packed["lm_head"] = packed.pop("wlm_head")
     if fp8 or fp4 or q4:

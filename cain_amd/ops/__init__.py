@@ -18,6 +18,7 @@ op                     source                      replaces (Ollama/llama.cpp)
 ``gemm_w8a8``          csrc/wgemm8.hip             fp8 weights x per-row fp8 activations, 16 < M <= 256
 ``gemm_w4``            csrc/gemm_w4.hip            the same GEMMs on MXFP4 (e2m1 + e8m0) weights, <= 64 rows
 ``gemm_q4``            csrc/gemm_q4.hip            the same GEMMs on GGUF Q4_0 / Q4_K blocks (exact values), any M
+``gemm_q6``            csrc/gemm_q6.hip            the same on GGUF Q6_K blocks (a Q4_K_M file's 6-bit tensors), any M
 ``rmsnorm``            csrc/norm.hip               RMSNorm (standalone; the engine fuses it)
 ``embed``              csrc/norm.hip               embedding gather (+Gemma scale)
 ``attention``          csrc/attention.hip          decode / prefill attention (split-K, in-kernel combine)
@@ -97,6 +98,9 @@ def load() -> ctypes.CDLL:
         lib.cain_gemm_q4.argtypes = ([ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp,
                                       vp] + [ci] * 5 + [vp])
         lib.cain_gemm_q4_rows.argtypes = [ci, ci]
+        lib.cain_gemm_q6.argtypes = ([ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp,
+                                      vp] + [ci] * 6 + [vp])
+        lib.cain_gemm_q6_rows.argtypes = [ci, ci]
         lib.cain_wgemm_inline.argtypes = [ci, ci, ci]
         lib.cain_wgemm_get_inline.argtypes = []
         lib.cain_gemm_w4_variant.argtypes = [ci, ci, ci, ci]
@@ -440,6 +444,49 @@ def gemm_q4(fmt: int, wq: torch.Tensor, sbuf: torch.Tensor, x: torch.Tensor, n: 
                           _p(r.get("kc")), _p(r.get("vtc")), r.get("H", 0), r.get("Hkv", 0), r.get("hd", 0), T_max,
                           epi, _stream())
     _check(rc, "gemm_q4")
+    _cmax_check(lib, cmax)
+    return out
+
+
+def gemm_q6(wq: torch.Tensor, sbuf: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16, bias=None,
+            out: Optional[torch.Tensor] = None, norm: bool = False, eps: float = 1e-6, rope=None, gain: bool = False,
+            cmax: Optional[torch.Tensor] = None, tile0: int = 0) -> torch.Tensor:
+    """GGUF Q6_K weight GEMM (``csrc/gemm_q6.hip``; any M, launches of the rows that fit): y = epi(B(x) @ W^T) with
+    W the blocks' exact values and (``wq``, ``sbuf``) = ``models.q4.pack_q6(...)``.  Epilogues EPI_BF16 / EPI_RESID
+    / EPI_F32 / EPI_QKV_ROPE; ``gain``, ``norm``, ``rope`` and ``cmax`` as ``gemm_q4``.  ``tile0``: the 16-row tile
+    the first of the ``n`` weight rows is in the epilogue's eyes -- output columns (``out`` then has at least 16
+    tile0 + n), ``bias`` (indexed from row 0 of the whole projection) and, under EPI_QKV_ROPE, the head or V row:
+    the V rows of a fused QKV projection run as a launch of their own with ``tile0 = (H + Hkv) hd / 16``."""
+    lib = load()
+    _gpu(wq, sbuf, x)
+    M, K = x.shape
+    assert x.dtype == torch.bfloat16 and x.stride(1) == 1 and M >= 1
+    assert wq.dtype == torch.uint8 and wq.shape[0] * 16 == n and wq.shape[1] * 128 == K, (tuple(wq.shape), K, n)
+    sc_bytes, dd_bytes = n * K // 16, n * K // 64
+    assert sbuf.dtype == torch.uint8 and sbuf.numel() == sc_bytes + dd_bytes + (4 * K if gain else 0)
+    assert epi in (EPI_BF16, EPI_RESID, EPI_F32, EPI_QKV_ROPE), "gemm_q6 has no gate/up activation epilogue"
+    n_out = 16 * tile0 + n
+    if epi == EPI_RESID:
+        assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
+    if epi == EPI_QKV_ROPE:
+        assert rope is not None and out is not None, "EPI_QKV_ROPE needs the rope/cache arguments and the q rows"
+    elif out is None:
+        out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
+    else:
+        assert out.shape[1] >= n_out
+    assert bias is None or bias.numel() >= n_out
+    r = rope or {}
+    T_max = r["kc"].shape[-2] if rope else 0
+    if rope and is_fp8_cache(r["kc"]):
+        epi |= EPI_KV_FP8
+    base = sbuf.data_ptr()
+    _cmax_set(lib, cmax, epi)
+    rc = lib.cain_gemm_q6(2, _p(wq), base, base + sc_bytes, (base + sc_bytes + dd_bytes) if gain else None,
+                          _p(x), x.stride(0), K, n, M, _p(out), out.stride(0), _p(bias), int(bool(norm)), eps,
+                          _p(r.get("slot")), _p(r.get("pos")), _p(r.get("cos_t")), _p(r.get("sin_t")),
+                          _p(r.get("kc")), _p(r.get("vtc")), r.get("H", 0), r.get("Hkv", 0), r.get("hd", 0), T_max,
+                          epi, int(tile0), _stream())
+    _check(rc, "gemm_q6")
     _cmax_check(lib, cmax)
     return out
 

@@ -40,6 +40,10 @@ CAIN_API int cain_gemm_q4(int fmt, const void* Wq, const void* sc, const void* d
                           int ldx, int K, int N, int M, void* Y, int ldy, const float* bias, int norm, float eps,
                           const int* slot, const int* pos, const float* cos_t, const float* sin_t, void* kc,
                           void* vtc, int H, int Hkv, int hd, int T_max, int epi_flags, hipStream_t st);
+CAIN_API int cain_gemm_q6(int fmt, const void* Wq, const void* sc, const void* dd, const float* gain, const void* X,
+                          int ldx, int K, int N, int M, void* Y, int ldy, const float* bias, int norm, float eps,
+                          const int* slot, const int* pos, const float* cos_t, const float* sin_t, void* kc,
+                          void* vtc, int H, int Hkv, int hd, int T_max, int epi_flags, int tile0, hipStream_t st);
 CAIN_API int cain_gemm_w8a8(const void* Wp8, const float* wscale, const void* X8, int ld8, const float* xs, int K,
                             int N, int M, void* Y, int ldy, const float* bias, const int* slot, const int* pos,
                             const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
@@ -81,6 +85,9 @@ extern "C" {
 
 // weight storage of a plan (CainPlanDesc::wfmt)
 enum { WFMT_BF16 = 0, WFMT_FP8 = 1, WFMT_FP4 = 2, WFMT_Q4_0 = 3, WFMT_Q4_K = 4 };
+// format of one matrix of a WFMT_Q4_* plan (CainLayer::f*, CainPlanDesc::flm_head): 0 = the plan's wfmt, else
+// WFMT_Q4_0 / WFMT_Q4_K or Q6_K (gemm_q6.hip: a Q4_K_M file's output head, attn_v and ffn_down tensors)
+enum { MFMT_PLAN = 0, MFMT_Q6_K = 5 };
 
 // RMSNorm gains are folded into the weight columns of the GEMM each norm feeds (attn_norm -> wqkv,
 // mlp_norm -> wgu, final_norm -> lm_head; models/weights.py fold_gain), so a norm is just a flag here.
@@ -101,6 +108,11 @@ struct CainLayer {
   const void* wo8;
   const void* wgu8;
   const void* wdown8;
+  // WFMT_Q4_* plans: each matrix's format (MFMT_*; 0: the plan's), and the V rows of the QKV projection packed on
+  // their own as Q6_K (null: V is inside wqkv, which then has all (H + 2 Hkv) hd rows)
+  int fqkv, fo, fgu, fdown;
+  const void* wv;
+  const void* sv;
 };
 
 struct CainPlanDesc {
@@ -140,6 +152,7 @@ struct CainPlanDesc {
   int x8_ld;
   // WFMT_Q4_*: 1 when each norm-fed weight's scale buffer ends with its fp32 RMSNorm gain (weights not gain-folded)
   int q4_gain;
+  int flm_head;  // WFMT_Q4_* plans: the LM head's format (MFMT_*; 0: the plan's)
 };
 
 struct CainRows {
@@ -199,7 +212,7 @@ int max_rows(const CainPlanDesc& d) {
 }
 
 // 5 launches per layer: QKV(+RMSNorm, bias, RoPE, KV append) -> attention(+combine) ->
-// O(+residual) -> gate/up(+RMSNorm, act*mul) -> down(+residual).
+// O(+residual) -> gate/up(+RMSNorm, act*mul) -> down(+residual); 6 in a layer whose V rows are Q6_K beside Q4 q / k.
 int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_sample, hipStream_t st) {
   const CainPlanDesc& d = p.d;
   const int qkv_dim = (d.H + 2 * d.Hkv) * d.hd;
@@ -207,23 +220,37 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
   const int epi_act = d.act_kind == 1 ? 4 : 3;
   // one GEMM of the schedule: the bf16 kernels (gemm.hip / wgemm.hip), fp8 weights (gemm_w8.hip / wgemm8.hip) or
   // MXFP4 weights (gemm_w4.hip)
+  // mf: the matrix's own format in a GGUF plan (MFMT_*); tile0: the first 16-row tile of N in the epilogue's eyes
+  // (Q6_K only: the V rows of a QKV projection launched on their own)
   auto gemm = [&](const void* W, const void* W8, const void* ws, const void* X, int ldx, int K, int N, void* Y,
-                  int ldy, const float* bias, int norm, const void* kc, const void* vc, int epi) -> int {
+                  int ldy, const float* bias, int norm, const void* kc, const void* vc, int epi, int mf = MFMT_PLAN,
+                  int tile0 = 0) -> int {
     void* kcm = const_cast<void*>(kc);
     void* vcm = const_cast<void*>(vc);
+    const bool gguf = d.wfmt == WFMT_Q4_0 || d.wfmt == WFMT_Q4_K;
+    if (gguf && mf == MFMT_Q6_K) {
+      // Q6_K (gemm_q6.hip): ws = [int8 group scales: N K / 16 bytes][fp32 d: N K / 64 bytes][the fp32 norm gain]
+      const char* sc = static_cast<const char*>(ws);
+      const char* dd = sc + (size_t)N * K / 16;
+      const float* gain = d.q4_gain && norm ? reinterpret_cast<const float*>(dd + (size_t)N * K / 64) : nullptr;
+      return cain_gemm_q6(2, W, sc, dd, gain, X, ldx, K, N, M, Y, ldy, bias, norm, d.eps, r.slot, r.pos, d.cos_t,
+                          d.sin_t, kcm, vcm, d.H, d.Hkv, d.hd, d.T_max, epi, tile0, st);
+    }
+    if (tile0 != 0 || (mf != MFMT_PLAN && !(gguf && (mf == WFMT_Q4_0 || mf == WFMT_Q4_K)))) return -1;
+    const int qf = gguf ? (mf == MFMT_PLAN ? d.wfmt : mf) : 0;
     if (d.wfmt == WFMT_FP4 && d.x8 && (M > g_w4a8_min_rows || M > 64) && cain_w8a8_eligible(N, K, M)) {  // W4A8
       CK(cain_quant_rows(X, ldx, K, M, d.x8, d.x8_ld, d.xs, norm, d.eps, st));
       return cain_gemm_w4a8(W, ws, d.x8, d.x8_ld, d.xs, K, N, M, Y, ldy, bias, r.slot, r.pos, d.cos_t, d.sin_t, kcm,
                             vcm, d.H, d.Hkv, d.hd, d.T_max, d.gemm_ws, d.gemm_ws_bytes, epi, st);
     }
-    if (d.wfmt == WFMT_Q4_0 || d.wfmt == WFMT_Q4_K) {
+    if (gguf) {
       // GGUF Q4_0 / Q4_K (gemm_q4.hip): ws = [block scales: N K / 16 bytes][Q4_K: (d, dmin): N K / 64 bytes]
       // [the fp32 norm gain over K, when the plan keeps gains unfolded (a GGUF file's exact values)]
       const char* sc = static_cast<const char*>(ws);
       const char* dd = sc + (size_t)N * K / 16;
-      const float* gain = d.q4_gain && norm ? reinterpret_cast<const float*>(dd + (d.wfmt == WFMT_Q4_K ? (size_t)N * K / 64 : 0))
+      const float* gain = d.q4_gain && norm ? reinterpret_cast<const float*>(dd + (qf == WFMT_Q4_K ? (size_t)N * K / 64 : 0))
                                             : nullptr;
-      return cain_gemm_q4(d.wfmt == WFMT_Q4_K, W, sc, dd, gain, X, ldx, K, N, M, Y, ldy, bias, norm, d.eps, r.slot,
+      return cain_gemm_q4(qf == WFMT_Q4_K, W, sc, dd, gain, X, ldx, K, N, M, Y, ldy, bias, norm, d.eps, r.slot,
                           r.pos, d.cos_t, d.sin_t, kcm, vcm, d.H, d.Hkv, d.hd, d.T_max, epi, st);
     }
     if (d.wfmt == WFMT_FP4)
@@ -247,14 +274,26 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
     const size_t kv_off = (size_t)l * d.kv_layer_elems * (d.kv8 ? 1 : 2);  // bytes
     char* kc = static_cast<char*>(d.kcache) + kv_off;
     char* vc = static_cast<char*>(d.vtcache) + kv_off;
-    CK(gemm(L.wqkv, L.wqkv8, L.sqkv, d.x, d.d, d.d, qkv_dim, d.q, q_dim, L.bqkv, 1, kc, vc,
-            /*EPI_QKV_ROPE*/ 5 | (d.kv8 ? /*EPI_KV_FP8*/ 0x100 : 0)));
+    const int epi_qkv = /*EPI_QKV_ROPE*/ 5 | (d.kv8 ? /*EPI_KV_FP8*/ 0x100 : 0);
+    if (L.wv) {
+      // V in Q6_K beside Q4 q / k rows (a Q4_K_M layer): two launches, both staging and normalising the activations
+      // -- the q and k rows with their RoPE and K append (the epilogue keys on H / Hkv / hd, not N), then the V rows
+      // with the tile offset that makes them the projection's V block
+      const int nqk = (d.H + d.Hkv) * d.hd;
+      CK(gemm(L.wqkv, nullptr, L.sqkv, d.x, d.d, d.d, nqk, d.q, q_dim, L.bqkv, 1, kc, vc, epi_qkv, L.fqkv));
+      CK(gemm(L.wv, nullptr, L.sv, d.x, d.d, d.d, qkv_dim - nqk, d.q, q_dim, L.bqkv, 1, kc, vc, epi_qkv, MFMT_Q6_K,
+              nqk / 16));
+    } else {
+      CK(gemm(L.wqkv, L.wqkv8, L.sqkv, d.x, d.d, d.d, qkv_dim, d.q, q_dim, L.bqkv, 1, kc, vc, epi_qkv, L.fqkv));
+    }
     CK(cain_attention_ex(d.q, kc, vc, r.slot, r.pos, d.part_o, d.part_ml, d.counters, d.attn, q_dim, M, d.H, d.Hkv,
                          d.hd, d.T_max, d.nsplit, d.attn_scale, d.kv8, 1.f, 1.f, st));
-    CK(gemm(L.wo, L.wo8, L.so, d.attn, q_dim, q_dim, d.d, d.x, d.d, nullptr, 0, nullptr, nullptr, /*EPI_RESID*/ 1));
-    CK(gemm(L.wgu, L.wgu8, L.sgu, d.x, d.d, d.d, 2 * d.ffn, d.act, d.ffn, nullptr, 1, nullptr, nullptr, epi_act));
+    CK(gemm(L.wo, L.wo8, L.so, d.attn, q_dim, q_dim, d.d, d.x, d.d, nullptr, 0, nullptr, nullptr, /*EPI_RESID*/ 1,
+            L.fo));
+    CK(gemm(L.wgu, L.wgu8, L.sgu, d.x, d.d, d.d, 2 * d.ffn, d.act, d.ffn, nullptr, 1, nullptr, nullptr, epi_act,
+            L.fgu));
     CK(gemm(L.wdown, L.wdown8, L.sdown, d.act, d.ffn, d.ffn, d.d, d.x, d.d, nullptr, 0, nullptr, nullptr,
-            /*EPI_RESID*/ 1));
+            /*EPI_RESID*/ 1, L.fdown));
   }
   if (want_logits) {
     // the LM head also writes the chunk maxima the chunk-max samplers start from (the bf16 skinny / wide kernels and
@@ -262,7 +301,7 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
     const int cm_mode = cain_sample_cm_enabled();
     if (p.cmax && (cm_mode == 1 || cm_mode == 3 || (cm_mode == 2 && M > 64))) cain_gemm_set_cmax(p.cmax);
     CK(gemm(d.lm_head, d.lm_head8, d.lm_head_scale, d.x, d.d, d.d, d.V, d.logits, d.V, nullptr, 1, nullptr, nullptr,
-            /*EPI_F32*/ 2));
+            /*EPI_F32*/ 2, d.flm_head));
   }
   const bool cm = want_logits && cain_gemm_cmax_take();
   if (want_sample) {

@@ -124,7 +124,7 @@ def cmd_convert(args: List[str]) -> None:
     ap = argparse.ArgumentParser(prog="python -m cain_amd convert")
     ap.add_argument("src", help="a Hugging Face checkpoint directory or a GGUF file")
     ap.add_argument("dst", help="the GGUF file to write")
-    ap.add_argument("--type", default="F16", choices=["F32", "F16", "BF16", "Q8_0", "Q4_0"])
+    ap.add_argument("--type", default="F16", choices=["F32", "F16", "BF16", "Q8_0", "Q4_0", "Q4_K", "Q6_K", "Q4_K_M"])
     ap.add_argument("--arch", default=None, choices=list(ARCHS),
                     help="GGUF architecture (default: from the checkpoint; Mistral is written as llama)")
     ns = ap.parse_args(args)
@@ -160,7 +160,7 @@ COMMANDS = {
     "analyze": ("<run_table.csv> [--out DIR]", cmd_analyze),
     "serve": ("[--host H] [--port P] [--models m1,m2] [--device N]", cmd_serve),
     "generate": ("--model M --prompt P [--num-predict N] [--checkpoint PATH]", cmd_generate),
-    "convert": ("<checkpoint dir | .gguf> <out.gguf> [--type F16|Q8_0|Q4_0|...]", cmd_convert),
+    "convert": ("<checkpoint dir | .gguf> <out.gguf> [--type F16|Q8_0|Q4_0|Q4_K|Q6_K|Q4_K_M|...]", cmd_convert),
     "help": ("", cmd_help),
 }
 

@@ -105,7 +105,7 @@ class Backend:
 
 
 # Ollama's quantization_level names for the engine's weight storage
-QUANT_LEVEL = {"bf16": "BF16", "fp8": "F8_E4M3", "fp4": "MXFP4"}
+QUANT_LEVEL = {"bf16": "BF16", "fp8": "F8_E4M3", "fp4": "MXFP4", "q4_0": "Q4_0", "q4_k": "Q4_K", "q4_k_m": "Q4_K_M"}
 
 
 def register_checkpoints(specs: Optional[List[str]]) -> List[str]:
@@ -660,7 +660,7 @@ def main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--fake-tok-s", type=float, default=2000.0, help="fake backend: modelled decode rate")
     ap.add_argument("--fake-prefill-s", type=float, default=0.0, help="fake backend: modelled time to first token")
     ap.add_argument("--trace-dir", default=None, help="write a torch.profiler Chrome trace of every decode batch here")
-    ap.add_argument("--weights", choices=["bf16", "fp8", "fp4"], default="bf16",
+    ap.add_argument("--weights", choices=list(QUANT_LEVEL), default="bf16",
                     help="GEMM weight storage (fp8: e4m3 per-row scaled; W8A8 above 16 rows, W8A16 below)")
     ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16", help="KV-cache storage (fp8: e4m3)")
     ap.add_argument("--static-batching", action="store_true",
@@ -700,7 +700,7 @@ def generate_main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--temperature", type=float, default=None)
     ap.add_argument("--seed", type=int, default=None)
-    ap.add_argument("--weights", choices=["bf16", "fp8", "fp4"], default="bf16")
+    ap.add_argument("--weights", choices=list(QUANT_LEVEL), default="bf16")
     ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16")
     ap.add_argument("--checkpoint", metavar="PATH", help="a Hugging Face checkpoint directory, served as --model")
     ns = ap.parse_args(argv)

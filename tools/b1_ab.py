@@ -61,7 +61,10 @@ def main() -> int:
                                  [dict(opts, seed=8 + t)])[0]
                 torch.cuda.synchronize()
                 rates.append(r.eval_count / (time.perf_counter() - t0))
-            rec = {"label": a.label, "sample_cm": a.sample_cm, "w4_split": a.w4_split, "model": model, "dtype": dtype, "tok_per_s": round(statistics.median(rates), 1),
+            # launches per decoded token: embed + 5 per layer (+ 1 where a Q6_K V runs behind Q4 q / k) + head + sampler
+            lay = eng._packed["layers"]
+            launches = 3 + 5 * len(lay) + sum("wv" in lp for lp in lay)
+            rec = {"label": a.label, "launches_per_token": launches, "sample_cm": a.sample_cm, "w4_split": a.w4_split, "model": model, "dtype": dtype, "tok_per_s": round(statistics.median(rates), 1),
                    "trials": [round(x, 1) for x in rates], "tokens": n_tok}
             print(json.dumps(rec), flush=True)
             if a.out:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""In-graph microbenchmark of the few-row weight-streaming GEMMs: MXFP4 (gemm_w4.hip, every kernel shape), fp8
-(gemm_w8.hip) and bf16 (gemm.hip) on a model's projection shapes at one row.
+"""In-graph microbenchmark of the few-row weight-streaming GEMMs: MXFP4 (gemm_w4.hip, every kernel shape), GGUF
+Q4_0 / Q4_K (gemm_q4.hip) and Q6_K (gemm_q6.hip; --dtypes q4_k,q6_k), fp8 (gemm_w8.hip) and bf16 (gemm.hip) on a
+model's projection shapes at one row.
 
 Each case captures `reps` calls into one hipGraph (torch.cuda.CUDAGraph) rotating over enough weight copies to
 exceed the 256 MiB Infinity Cache, replays it, and reports time per call and weight bytes / time -- the
@@ -87,7 +88,8 @@ def main() -> int:
         out = torch.zeros(M, n_out, device=dev, dtype=torch.float32 if epi == ops.EPI_F32 else torch.bfloat16)
         rp = rope if epi == ops.EPI_QKV_ROPE else None
         for dt, cp in [(dt, cp) for dt in ns.dtypes.split(",") for cp in ns.copies.split(",")]:
-            bpp = {"fp4": 0.5 + 1 / 32, "fp8": 1.0, "bf16": 2.0, "q4_0": 0.5 + 1 / 16, "q4_k": 0.5 + 1 / 16 + 1 / 64}[dt]
+            bpp = {"fp4": 0.5 + 1 / 32, "fp8": 1.0, "bf16": 2.0, "q4_0": 0.5 + 1 / 16, "q4_k": 0.5 + 1 / 16 + 1 / 64,
+                   "q6_k": 0.75 + 1 / 16 + 1 / 64}[dt]
             wbytes = int(N * K * bpp)
             ncopy = int(cp) if int(cp) > 0 else max(2, min(16, (768 << 20) // max(1, wbytes) + 1))
             if dt == "fp4":
@@ -126,6 +128,23 @@ def main() -> int:
                 def fn(i, ws=ws):
                     wq, sb = ws[i % len(ws)]
                     ops.gemm_q4(fmt, wq, sb, xk, N, epi, out=out, norm=norm, rope=rp)
+                us = graph_time(fn)
+                print(json.dumps(dict(role=role, dtype=dt, N=N, K=K, M=M, us=round(us, 2),
+                                      TBps=round(wbytes / us / 1e6, 2))), flush=True)
+            elif dt == "q6_k":
+                if epi in (ops.EPI_SILU, ops.EPI_GELU):
+                    continue  # gemm_q6.hip has no gate/up activation epilogue
+                # random codes, int8 group scales 1 and d = 2^-5: finite values
+                def rnd_sb6():
+                    sb = torch.ones(N * K // 16 + N * K // 64, device=dev, dtype=torch.uint8)
+                    sb[N * K // 16:].view(torch.float32)[:] = 2.0 ** -5
+                    return sb
+                ws = [(torch.randint(0, 256, (N // 16, K // 128, 1536), device=dev, dtype=torch.uint8), rnd_sb6())
+                      for _ in range(ncopy)]
+
+                def fn(i, ws=ws):
+                    wq, sb = ws[i % len(ws)]
+                    ops.gemm_q6(wq, sb, xk, N, epi, out=out, norm=norm, rope=rp)
                 us = graph_time(fn)
                 print(json.dumps(dict(role=role, dtype=dt, N=N, K=K, M=M, us=round(us, 2),
                                       TBps=round(wbytes / us / 1e6, 2))), flush=True)
