@@ -125,6 +125,7 @@ def load() -> ctypes.CDLL:
         lib.cain_attention_ex.argtypes = ([vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, ci, cf, cf]
                                           + [vp])
         lib.cain_attention_set_ring.argtypes = [ci]
+        lib.cain_attention_set_body.argtypes = [ci]
         lib.cain_sample.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]
         lib.cain_sample_cm.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]
         lib.cain_sample_lean.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]
@@ -769,6 +770,16 @@ def set_attention_ring(variant: int) -> None:
     one split, 2 to 64 (row, kv head) pairs per CU): 0 off (the register kernel), 1 on (the default).  A/B switch
     for tests and profiles, read at every launch and graph capture."""
     load().cain_attention_set_ring(int(variant))
+
+
+def set_attention_body(v: int) -> None:
+    """Register-kernel body of the decode attention at head_dim <= 128 (csrc/attention.hip attn_decode_kernel;
+    head_dim 256 always runs its one-set body): 2 one register set of K / V fragments held to 128 registers (the
+    default), 1 one set at 3 waves per SIMD, 0 two sets ping-pong with a clamped prefetch.  A/B switch for tests
+    and profiles, read at every launch and graph capture."""
+    if int(v) not in (0, 1, 2):
+        raise ValueError(f"attention body {v}: 0, 1 or 2")
+    load().cain_attention_set_body(int(v))
 
 
 SAMPLE_DTYPE = [("temperature", "f4"), ("top_p", "f4"), ("repeat_penalty", "f4"), ("top_k", "i4"),

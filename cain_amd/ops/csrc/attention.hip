@@ -37,6 +37,13 @@
 // barrier -> relaxed agent ticket; no release/acquire fences, counter reset by the
 // reducer: cdna_hip_programming.md §5 'In-launch split-K reduction'), so there
 // is no separate combine launch.
+//
+// The cache past a row's length must hold FINITE values: the row's last partial block is loaded whole and its
+// positions t >= L enter the PV product with p = 0 exactly (score -inf), so the kernel computes 0 * V[t] -- 0 for
+// any finite V[t], NaN for an Inf or NaN.  (K past the length only feeds scores that the mask replaces.)  The
+// engine's caches start as zeros and are only ever overwritten with finite values; tests/attn_exact.py fills the
+// tail with large finite values on purpose.  A row with slot < 0 reads no cache and gets a zero output row from
+// both bodies (the register kernel's merge finds l = 0; the ring's compute wave writes zeros).
 #include <cstdlib>
 #include <type_traits>
 
