@@ -101,6 +101,11 @@ def load() -> ctypes.CDLL:
         lib.cain_gemm_q6.argtypes = ([ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp,
                                       vp] + [ci] * 6 + [vp])
         lib.cain_gemm_q6_rows.argtypes = [ci, ci]
+        lib.cain_gemm_q_set_tile.argtypes = [ci]
+        lib.cain_gemm_q_set_tile.restype = None
+        lib.cain_gemm_q_set_tile_nb.argtypes = [ci]
+        lib.cain_gemm_q_set_tile_nb.restype = None
+        lib.cain_gemm_q_passes.argtypes = [ci, ci, ci, ci]
         lib.cain_wgemm_inline.argtypes = [ci, ci, ci]
         lib.cain_wgemm_get_inline.argtypes = []
         lib.cain_gemm_w4_variant.argtypes = [ci, ci, ci, ci]
@@ -415,7 +420,8 @@ def _cmax_check(lib, cmax) -> None:
 def gemm_q4(fmt: int, wq: torch.Tensor, sbuf: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16,
             bias=None, out: Optional[torch.Tensor] = None, norm: bool = False, eps: float = 1e-6, rope=None,
             gain: bool = False, cmax: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """GGUF Q4_0 (``fmt`` 0) / Q4_K (1) weight GEMM (``csrc/gemm_q4.hip``; any M, 16-row launches): y = epi(B(x) @
+    """GGUF Q4_0 (``fmt`` 0) / Q4_K (1) weight GEMM (``csrc/gemm_q4.hip``; any M: rows beyond the stream kernel's LDS
+    copy run on ``csrc/gemm_qtile.hip``, one pass over the weights per 64 rows, see ``set_q_tile``): y = epi(B(x) @
     W^T) with W the blocks' exact values and (``wq``, ``sbuf``) = ``models.q4.pack_q4(...)``; ``gain``: the scale
     buffer ends with the fp32 RMSNorm gain, applied to the activations (``norm`` must be set).  Same epilogues,
     RMSNorm fusion and ``rope`` arguments as ``gemm_w8``."""
@@ -452,7 +458,8 @@ def gemm_q4(fmt: int, wq: torch.Tensor, sbuf: torch.Tensor, x: torch.Tensor, n: 
 def gemm_q6(wq: torch.Tensor, sbuf: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16, bias=None,
             out: Optional[torch.Tensor] = None, norm: bool = False, eps: float = 1e-6, rope=None, gain: bool = False,
             cmax: Optional[torch.Tensor] = None, tile0: int = 0) -> torch.Tensor:
-    """GGUF Q6_K weight GEMM (``csrc/gemm_q6.hip``; any M, launches of the rows that fit): y = epi(B(x) @ W^T) with
+    """GGUF Q6_K weight GEMM (``csrc/gemm_q6.hip``; any M: rows beyond the stream kernel's LDS copy run on
+    ``csrc/gemm_qtile.hip``, one pass over the weights per 64 rows, see ``set_q_tile``): y = epi(B(x) @ W^T) with
     W the blocks' exact values and (``wq``, ``sbuf``) = ``models.q4.pack_q6(...)``.  Epilogues EPI_BF16 / EPI_RESID
     / EPI_F32 / EPI_QKV_ROPE; ``gain``, ``norm``, ``rope`` and ``cmax`` as ``gemm_q4``.  ``tile0``: the 16-row tile
     the first of the ``n`` weight rows is in the epilogue's eyes -- output columns (``out`` then has at least 16
@@ -490,6 +497,26 @@ def gemm_q6(wq: torch.Tensor, sbuf: torch.Tensor, x: torch.Tensor, n: int, epi: 
     _check(rc, "gemm_q6")
     _cmax_check(lib, cmax)
     return out
+
+
+def set_q_tile(mode: int) -> None:
+    """Path of the GGUF GEMMs (``gemm_q4`` / ``gemm_q6`` and the runtime's): -1 the rule (the many-row tile kernels of
+    ``csrc/gemm_qtile.hip`` where they measured faster than the few-row stream kernels: from 17 rows, and from 8 rows
+    where the stream kernels need 4 or more passes; profiles/r8/q_tile/README.md), 0 never the tile kernels (M rows as
+    ceil(M / rows) stream launches), 1 always (also M = 1).  Read at every launch and graph capture.  Tests / tuning."""
+    load().cain_gemm_q_set_tile(int(mode))
+
+
+def set_q_tile_nb(nb: int) -> None:
+    """Row blocks per wave of the Q4 tile kernels (1 or 2; 0: the rule, gemm_qtile.hip q_tile_nb; Q6_K has 1 only).
+    Tests reach both instances at small N with it; tuning."""
+    load().cain_gemm_q_set_tile_nb(int(nb))
+
+
+def gemm_q_passes(fmt: int, k: int, m: int, epi: int = EPI_BF16) -> int:
+    """How many times a GGUF GEMM of ``m`` rows streams its weight matrix under the current ``set_q_tile`` mode
+    (``fmt`` 0 Q4_0, 1 Q4_K, 2 Q6_K); -1 where the entry refuses the shape (K too long for the stream rows)."""
+    return int(load().cain_gemm_q_passes(int(fmt), int(k), int(m), int(epi)))
 
 
 def _w4_ws(device, nbytes: int) -> torch.Tensor:

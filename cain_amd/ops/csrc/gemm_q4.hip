@@ -1,5 +1,6 @@
 // GGUF 4-bit weights (llama.cpp's Q4_0 and Q4_K, Ollama's default model builds) for single-stream / few-row
-// decode, M <= 16 rows per launch: the weights' VALUES as the file stores them, only their layout repacked.
+// decode, M <= 16 rows per launch (many rows: gemm_qtile.hip): the weights' VALUES as the file stores them, only
+// their layout repacked.
 //
 // The reference's models are Ollama pulls (/root/reference/README.md:29-30, tags of
 // /root/reference/experiment/RunnerConfig.py:80), whose default builds are GGUF Q4_0 / Q4_K_M.
@@ -38,39 +39,13 @@
 
 #include "common.h"
 #include "gemm_epi.h"
-
-enum { Q4F_0 = 0, Q4F_K = 1 };
-
-typedef uint32_t q4u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t q4u32x2 __attribute__((ext_vector_type(2)));
+#include "gemm_q.h"
 
 struct Q4Args {
   const uint8_t* sc;   // Q4_0: fp16 d; Q4_K: (sc | m << 8) -- [tiles][KQ][16 rows][4 blocks] x 2 bytes
   const uint32_t* dd;  // Q4_K: (d, dmin) fp16 pairs [tiles][KQ / 2][16 rows]
   const float* gain;   // RMSNorm gain per k applied while staging (null: none)
 };
-
-// four codes (one byte lane per k: low nibble k = j, high nibble k = j + 4, j = 0..3) -> bf16 128 + q, k order
-__device__ __forceinline__ bf16x8 q4_frag(uint32_t w) {
-  const uint32_t lo = w & 0x0f0f0f0fu, hi = (w >> 4) & 0x0f0f0f0fu;
-  // v_perm_b32 selector bytes: 0-3 pick the second operand's bytes, 4-7 the first's; 0x43 is bf16 128's high byte
-  constexpr uint32_t C43 = 0x43434343u;
-  const uint32_t p0 = __builtin_amdgcn_perm(C43, lo, 0x05010400u);  // k0, k1: [lo.b0, 43, lo.b1, 43]
-  const uint32_t p1 = __builtin_amdgcn_perm(C43, lo, 0x05030402u);  // k2, k3
-  const uint32_t p2 = __builtin_amdgcn_perm(C43, hi, 0x05010400u);  // k4, k5
-  const uint32_t p3 = __builtin_amdgcn_perm(C43, hi, 0x05030402u);  // k6, k7
-  return __builtin_bit_cast(bf16x8, q4u32x4{p0, p1, p2, p3});
-}
-
-__device__ __forceinline__ float q4_h2f(uint32_t h) { return float(__builtin_bit_cast(_Float16, (uint16_t)h)); }
-
-// sum over the 4 lanes of a quad (4j .. 4j + 3) by two DPP quad permutations (xor 1, xor 2): no LDS round trip (the
-// ds_bpermute of __shfl_xor cost ~6 % of qwen2:1.5b's batch-1 rate in the staging); every lane gets the same value
-__device__ __forceinline__ float q4_quad_sum(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, false));
-  return v;
-}
 
 __device__ __forceinline__ void q4_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -331,7 +306,8 @@ CAIN_API int cain_gemm_q4_rows(int K, int epi) { return q4_rows(K, epi & EPI_MAS
 CAIN_API float* cain_gemm_cmax_claim(int N);  // gemm.hip
 
 // Same GEMM arguments as cain_gemm_w4 (gemm_w4.hip) plus the format (0 Q4_0, 1 Q4_K), its scale arrays and the
-// RMSNorm gain to apply to the activations (null: none).  M > 16 (a prefill chunk) runs as 16-row launches.
+// RMSNorm gain to apply to the activations (null: none).  More rows than the LDS copy holds (cain_gemm_q4_rows) run
+// on the tile kernel of gemm_qtile.hip, 64 rows per launch (cain_gemm_q_set_tile(0): as several stream launches).
 CAIN_API int cain_gemm_q4(int fmt, const void* Wq, const void* sc, const void* dd, const float* gain, const void* X,
                           int ldx, int K, int N, int M, void* Y, int ldy, const float* bias, int norm, float eps,
                           const int* slot, const int* pos, const float* cos_t, const float* sin_t, void* kc,
@@ -343,9 +319,13 @@ CAIN_API int cain_gemm_q4(int fmt, const void* Wq, const void* sc, const void* d
   if (rows == 0) return -1;
   const int n_cu = cain_cu_budget();
   float* cm = epi == EPI_F32 ? cain_gemm_cmax_claim(N) : nullptr;  // the LM head: the sampler's chunk maxima too
-  for (int m0 = 0; m0 < M; m0 += rows) {
-    const int mc = std::min(rows, M - m0);
-    const int waves = q4_waves(K, mc, epi);  // > 0: mc <= rows
+  // many rows (q_tile_selected: more than one pass of the stream kernel, by default): 64 rows per launch of the tile
+  // kernel (gemm_qtile.hip), one pass over the weights each
+  const bool tile = q_tile_selected(fmt, K, M, epi, rows);
+  const int per = tile ? 64 : rows;
+  for (int m0 = 0; m0 < M; m0 += per) {
+    const int mc = std::min(per, M - m0);
+    const int waves = tile ? 4 : q4_waves(K, mc, epi);  // > 0: mc <= rows
     GemmArgs a{};
     a.Wp = reinterpret_cast<const bf16x8*>(Wq);
     a.X = reinterpret_cast<const __bf16*>(X) + (size_t)m0 * ldx;
@@ -358,6 +338,11 @@ CAIN_API int cain_gemm_q4(int fmt, const void* Wq, const void* sc, const void* d
     a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = (epi_flags & EPI_KV_FP8) ? 1 : 0;
     a.msplit = 1;
     if (cm) a.cmax = cm + (size_t)m0 * (N / 16), a.ld_cm = N / 16;
+    if (tile) {
+      const hipError_t e = q_tile_launch(fmt, a, sc, dd, gain, epi, norm != 0, 0, st);
+      if (e != hipSuccess) return int(e);
+      continue;
+    }
     const Q4Args q{static_cast<const uint8_t*>(sc), static_cast<const uint32_t*>(dd), gain};
     const int npairs = N / 16;
     const int grid = std::min(npairs, n_cu * (waves == 8 ? 2 : 4));

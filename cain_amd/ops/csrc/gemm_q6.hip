@@ -28,38 +28,13 @@
 
 #include "common.h"
 #include "gemm_epi.h"
-
-enum { Q6F_K = 2 };  // models/q4.py Q6_K
-
-typedef uint32_t q6u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t q6u32x2 __attribute__((ext_vector_type(2)));
-typedef short q6s16x4 __attribute__((ext_vector_type(4)));
+#include "gemm_q.h"
 
 struct Q6Args {
   const uint8_t* sc;  // int8 group scales [tiles][KQ][16 rows][8 groups]
   const float* d;     // super-block scales [tiles][KQ / 2][16 rows]
   const float* gain;  // RMSNorm gain per k applied while staging (null: none)
 };
-
-// the 4 codes of MFMA s (bytes j = 0..3 of one low and one high dword) -> bf16 128 + q, k order
-__device__ __forceinline__ q6s16x4 q6_frag(const q6u32x4& lo, const q6u32x2& hi, int s) {
-  const uint32_t l = (lo[s >> 1] >> (4 * (s & 1))) & 0x0f0f0f0fu;
-  const int sh = 2 * (s & 3);  // the pair's bit position; it goes to bits 4..5 of its byte
-  const uint32_t h = (sh <= 4 ? hi[s >> 2] << (4 - sh) : hi[s >> 2] >> (sh - 4)) & 0x30303030u;
-  const uint32_t b = l | h;
-  // v_perm_b32 selector bytes: 0-3 pick the second operand's bytes, 4-7 the first's; 0x43 is bf16 128's high byte
-  constexpr uint32_t C43 = 0x43434343u;
-  const uint32_t p0 = __builtin_amdgcn_perm(C43, b, 0x05010400u);  // k0, k1
-  const uint32_t p1 = __builtin_amdgcn_perm(C43, b, 0x05030402u);  // k2, k3
-  return __builtin_bit_cast(q6s16x4, q6u32x2{p0, p1});
-}
-
-__device__ __forceinline__ float q6_i8f(uint32_t w, int byte) { return float(int(int8_t(w >> (8 * byte)))); }
-
-// sum over the 2 lanes of a pair (2j, 2j + 1) by one DPP quad permutation (xor 1); both lanes get the same value
-__device__ __forceinline__ float q6_pair_sum(float v) {
-  return v + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-}
 
 __device__ __forceinline__ void q6_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -321,16 +296,20 @@ CAIN_API int cain_gemm_q6(int fmt, const void* Wq, const void* sc, const void* d
   if (epi == EPI_QKV_ROPE && (hd % 16 || (hd / 2) % 8)) return -1;
   const int rows = q6_rows(K, epi);
   if (rows == 0) return -1;
-  for (int m0 = 0; m0 < M; m0 += rows) {  // every launch's rows must fit before the first is made
+  // many rows (q_tile_selected: more than one pass of the stream kernel, by default): 64 rows per launch of the tile
+  // kernel (gemm_qtile.hip), one pass over the weights each
+  const bool tile = q_tile_selected(fmt, K, M, epi, rows);
+  const int per = tile ? 64 : rows;
+  for (int m0 = 0; !tile && m0 < M; m0 += rows) {  // every launch's rows must fit before the first is made
     const int mc = std::min(rows, M - m0);
     const int waves = q6_waves(K, mc, epi);
     if (waves == 0 || q6_lds_need(mc, K) > (waves == 8 ? q6_xl_bytes<8>() : q6_xl_bytes<4>())) return -1;
   }
   const int n_cu = cain_cu_budget();
   float* cm = (epi == EPI_F32 && tile0 == 0) ? cain_gemm_cmax_claim(N) : nullptr;  // the LM head's chunk maxima
-  for (int m0 = 0; m0 < M; m0 += rows) {
-    const int mc = std::min(rows, M - m0);
-    const int waves = q6_waves(K, mc, epi);
+  for (int m0 = 0; m0 < M; m0 += per) {
+    const int mc = std::min(per, M - m0);
+    const int waves = tile ? 4 : q6_waves(K, mc, epi);
     GemmArgs a{};
     a.Wp = reinterpret_cast<const bf16x8*>(Wq);
     a.X = reinterpret_cast<const __bf16*>(X) + (size_t)m0 * ldx;
@@ -343,6 +322,11 @@ CAIN_API int cain_gemm_q6(int fmt, const void* Wq, const void* sc, const void* d
     a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = (epi_flags & EPI_KV_FP8) ? 1 : 0;
     a.msplit = 1;
     if (cm) a.cmax = cm + (size_t)m0 * (N / 16), a.ld_cm = N / 16;
+    if (tile) {
+      const hipError_t e = q_tile_launch(fmt, a, sc, dd, gain, epi, norm != 0, tile0, st);
+      if (e != hipSuccess) return int(e);
+      continue;
+    }
     const Q6Args q{static_cast<const uint8_t*>(sc), static_cast<const float*>(dd), gain};
     const int npairs = N / 16;
     const int grid = std::min(npairs, n_cu * (waves == 8 ? 2 : 4));

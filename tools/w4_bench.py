@@ -59,7 +59,56 @@ def main() -> int:
     ap.add_argument("--copies", default="0",
                     help="weight copies rotated per call, comma list: 0 = enough to exceed the 256 MiB Infinity Cache "
                          "(cold, as in decode); 1 = one copy (cache-hot); e.g. 8 = Infinity-Cache-hot, beyond L2")
+    ap.add_argument("--q-tile", default="-1",
+                    help="GGUF dtypes (q4_0, q4_k, q6_k): ops.set_q_tile modes, comma list of -1 (the rule), 0 (stream "
+                         "kernels only), 1 (tile kernels always): one captured graph per mode on the same weight "
+                         "copies, replayed in turn (interleaved), median per mode")
+    ap.add_argument("--q-tile-nb", default="0",
+                    help="row blocks per wave of the tile kernels for the modes that use them, comma list (0: the rule)")
+    ap.add_argument("--q6-everywhere", action="store_true",
+                    help="time q6_k on every role (default: only down and lm_head, the whole matrices Q4_K_M keeps in Q6_K)")
+    ap.add_argument("--reps", type=int, default=40, help="calls per captured graph (fewer for many-pass shapes)")
     ns = ap.parse_args()
+    q_modes = [int(v) for v in ns.q_tile.split(",")]
+    q_nbs = [int(v) for v in ns.q_tile_nb.split(",")]
+
+    def q_time(fn, dt, role, N, K, wbytes, fmt_id, epi, rounds: int = 5):
+        """One GGUF case under every (--q-tile mode, --q-tile-nb): the graphs are captured first, then replayed in
+        turn for ``rounds`` rounds; the median per graph is reported, with GB/s of weight bytes."""
+        cases = [(m, nb) for m in q_modes for nb in (q_nbs if m != 0 else q_nbs[:1])]
+        graphs = []
+        for mode, nb in cases:  # the path is chosen at capture
+            ops.set_q_tile(mode)
+            ops.set_q_tile_nb(nb)
+            passes = ops.gemm_q_passes(fmt_id, K, M, epi)
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                fn(0)
+            torch.cuda.current_stream().wait_stream(s)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for i in range(ns.reps):
+                    fn(i)
+            g.replay()
+            torch.cuda.synchronize()
+            graphs.append((mode, nb, passes, g, []))
+        ops.set_q_tile(-1)
+        ops.set_q_tile_nb(0)
+        for _ in range(rounds):
+            for _, _, _, g, ts in graphs:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                g.replay()
+                b.record()
+                torch.cuda.synchronize()
+                ts.append(a.elapsed_time(b) / ns.reps * 1e3)
+        for mode, nb, passes, _, ts in graphs:
+            us = sorted(ts)[len(ts) // 2]
+            print(json.dumps(dict(role=role, dtype=dt, N=N, K=K, M=M, q_tile=mode, nb=nb, passes=passes,
+                                  us=round(us, 2), GBps=round(wbytes / us / 1e3, 1),
+                                  TBps=round(wbytes / us / 1e6, 2))), flush=True)
     cfg = get_config(ns.model)
     dev = torch.device("cuda")
     d, F = cfg.d_model, cfg.ffn
@@ -128,12 +177,12 @@ def main() -> int:
                 def fn(i, ws=ws):
                     wq, sb = ws[i % len(ws)]
                     ops.gemm_q4(fmt, wq, sb, xk, N, epi, out=out, norm=norm, rope=rp)
-                us = graph_time(fn)
-                print(json.dumps(dict(role=role, dtype=dt, N=N, K=K, M=M, us=round(us, 2),
-                                      TBps=round(wbytes / us / 1e6, 2))), flush=True)
+                q_time(fn, dt, role, N, K, wbytes, fmt, epi)
             elif dt == "q6_k":
                 if epi in (ops.EPI_SILU, ops.EPI_GELU):
                     continue  # gemm_q6.hip has no gate/up activation epilogue
+                if role not in ("down", "lm_head") and not ns.q6_everywhere:
+                    continue  # a Q4_K_M file keeps these matrices in Q4_K (of QKV only the V rows are Q6_K)
                 # random codes, int8 group scales 1 and d = 2^-5: finite values
                 def rnd_sb6():
                     sb = torch.ones(N * K // 16 + N * K // 64, device=dev, dtype=torch.uint8)
@@ -145,9 +194,7 @@ def main() -> int:
                 def fn(i, ws=ws):
                     wq, sb = ws[i % len(ws)]
                     ops.gemm_q6(wq, sb, xk, N, epi, out=out, norm=norm, rope=rp)
-                us = graph_time(fn)
-                print(json.dumps(dict(role=role, dtype=dt, N=N, K=K, M=M, us=round(us, 2),
-                                      TBps=round(wbytes / us / 1e6, 2))), flush=True)
+                q_time(fn, dt, role, N, K, wbytes, 2, epi)
             elif dt == "fp8":
                 ws = [(torch.randint(0, 120, (N // 16, K // 64, 64, 16), device=dev, dtype=torch.uint8),
                        torch.full((N,), 0.01, device=dev)) for _ in range(ncopy)]
