@@ -18,6 +18,8 @@ Backends
 Batching: up to ``max_batch`` (≤ 256) sequences decode together ("trial
 batching") — each row has its own cache slot, position, budget
 and sampling options; rows that finish early idle until the batch ends.
+(An idle row keeps its last position and token, so each later step rewrites that one KV position with the last
+generated token's K / V: harmless, nothing reads it again; tests/engine_state.py expected_inputs encodes it.)
 Prefill: every prompt token but the last goes through the same forward as
 ≤128-row chunks (rows carry their own slot/position, so the decode attention
 kernel doubles as causal prefill attention); the last prompt token is the
