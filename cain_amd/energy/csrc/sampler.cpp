@@ -405,10 +405,17 @@ struct Sampler {
     ring[idx] = s;
   }
 
-  void poll_energy(GpuTrack& g, uint64_t t) {
+  // One reading of the accumulator.  The host time of a point is taken after the read returns, so the reading is
+  // never newer than its stamp however long the call took: min(host - dev) is then an upper estimate of the
+  // clock offset that a slow call cannot pull below the truth.
+  // A backwards step of the accumulator (a counter reset; its modulus is not documented) adds nothing: the
+  // energy of the one update interval that ends at the step is lost, and a window that crosses it reads that
+  // much low, never negative and never high (tests/test_energy_trace.py).
+  void poll_energy(GpuTrack& g) {
     uint64_t acc = 0, dev_ts = 0;
     float res = 0;
     if (!read_energy(g.smi_index, &acc, &res, &dev_ts)) return;
+    const uint64_t t = now_ns();
     std::lock_guard<std::mutex> l(mu);
     if (!g.have) {
       g.have = true;
@@ -416,7 +423,7 @@ struct Sampler {
       g.res_uj = res;
       g.trace.push_back({t, dev_ts, 0.0});
     } else if (acc != g.last_acc) {
-      uint64_t delta = acc >= g.last_acc ? acc - g.last_acc : 0;  // wrap: ignore the step
+      uint64_t delta = acc >= g.last_acc ? acc - g.last_acc : 0;  // backwards: this interval's energy is lost
       g.joules += double(delta) * double(res) * 1e-6;
       g.last_acc = acc;
       g.trace.push_back({t, dev_ts, g.joules});
@@ -507,7 +514,7 @@ struct Sampler {
     uint64_t next_slow = now_ns();
     while (running.load(std::memory_order_acquire)) {
       uint64_t t = now_ns();
-      for (auto& g : gpus) poll_energy(g, t);
+      for (auto& g : gpus) poll_energy(g);
       if (t >= next_slow) {
         slow_sample(t);
         next_slow += uint64_t(period_us) * 1000ull;
@@ -518,26 +525,50 @@ struct Sampler {
     }
   }
 
-  // cumulative joules of gpu slot at host time t (linear interpolation on the trace)
-  double joules_at(const GpuTrack& g, uint64_t t) const {
+  // Host time at which each trace point is used: its device timestamp mapped to host time (dev + the minimum
+  // observed host - dev), else the time it was observed.  The mapping is used only while it looks sane:
+  //  * over the whole trace the device clock advances at the host's rate (a timestamp in another unit is off by
+  //    10x or more; the trace then runs on observation times, as it does without timestamps);
+  //  * the point, or one of its neighbours, was observed less than 50 ms after its mapped time.  A single point
+  //    seen late (one slow amd-smi call) keeps its mapped time, which is the right one; when every point is late
+  //    the offset estimate has drifted and observation times take over.
+  // Times are clamped to their predecessor's, so the sequence is non-decreasing whatever mix results: the
+  // interpolation's binary search needs that, and windows are additive only then.
+  std::vector<double> used_times(const GpuTrack& g) const {
+    const auto& tr = g.trace;
+    const size_t n = tr.size();
+    std::vector<double> u(n), late(n, INFINITY);
+    bool sane = g.best_offset != INT64_MAX;
+    if (sane && n >= 2 && tr.front().dev_ns && tr.back().dev_ns) {
+      const double dh = double(tr.back().host_ns - tr.front().host_ns);
+      const double dd = double(int64_t(tr.back().dev_ns - tr.front().dev_ns));
+      sane = dd > 0.5 * dh && dd < 2.0 * dh;
+    }
+    if (sane)
+      for (size_t i = 0; i < n; ++i)
+        if (tr[i].dev_ns) late[i] = double(tr[i].host_ns) - double(int64_t(tr[i].dev_ns) + g.best_offset);
+    double prev = 0;
+    for (size_t i = 0; i < n; ++i) {
+      double h = double(tr[i].host_ns);
+      const double near = std::min({late[i], i ? late[i - 1] : INFINITY, i + 1 < n ? late[i + 1] : INFINITY});
+      if (late[i] >= -1e3 && near < 50e6) h -= late[i];
+      u[i] = prev = std::max(prev, h);
+    }
+    return u;
+  }
+
+  // cumulative joules of gpu slot at host time t (linear interpolation on the trace; u = used_times(g))
+  double joules_at(const GpuTrack& g, const std::vector<double>& u, uint64_t t) const {
     const auto& tr = g.trace;
     if (tr.empty()) return NAN;
-    auto host_of = [&](const TracePoint& p) -> double {
-      // device timestamp mapped to host time when the offset estimate is sane
-      if (p.dev_ns && g.best_offset != INT64_MAX) {
-        double h = double(int64_t(p.dev_ns) + g.best_offset);
-        if (h <= double(p.host_ns) + 1e3 && double(p.host_ns) - h < 50e6) return h;
-      }
-      return double(p.host_ns);
-    };
     double tt = double(t);
-    if (tt <= host_of(tr.front())) return tr.front().joules;
-    if (tt >= host_of(tr.back())) {
+    if (tt <= u.front()) return tr.front().joules;
+    if (tt >= u.back()) {
       // extrapolate with the last segment's slope (bounded to one counter interval)
       if (tr.size() < 2) return tr.back().joules;
       const auto& a = tr[tr.size() - 2];
       const auto& b = tr.back();
-      double ha = host_of(a), hb = host_of(b);
+      double ha = u[u.size() - 2], hb = u.back();
       if (hb <= ha) return b.joules;
       double slope = (b.joules - a.joules) / (hb - ha);
       double span = std::min(tt - hb, hb - ha);
@@ -546,12 +577,12 @@ struct Sampler {
     size_t lo = 0, hi = tr.size() - 1;
     while (hi - lo > 1) {
       size_t mid = (lo + hi) / 2;
-      if (host_of(tr[mid]) <= tt)
+      if (u[mid] <= tt)
         lo = mid;
       else
         hi = mid;
     }
-    double ha = host_of(tr[lo]), hb = host_of(tr[hi]);
+    double ha = u[lo], hb = u[hi];
     if (hb <= ha) return tr[hi].joules;
     double f = (tt - ha) / (hb - ha);
     // energy reported at point hi accrued over (ha, hb]
@@ -612,7 +643,7 @@ int es_start(void* h) {
   s->t_start = now_ns();
   read_cpu_times(&s->last_cpu);
   s->host.poll();  // first reading: the zero of the cumulative host joules
-  for (auto& g : s->gpus) s->poll_energy(g, s->t_start);
+  for (auto& g : s->gpus) s->poll_energy(g);
   s->running.store(true, std::memory_order_release);
   s->th = std::thread([s] { s->loop(); });
   return 0;
@@ -623,8 +654,7 @@ int es_stop(void* h) {
   if (!s || !s->running.load()) return -1;
   s->running.store(false, std::memory_order_release);
   if (s->th.joinable()) s->th.join();
-  uint64_t t = now_ns();
-  for (auto& g : s->gpus) s->poll_energy(g, t);
+  for (auto& g : s->gpus) s->poll_energy(g);
   return 0;
 }
 
@@ -641,7 +671,8 @@ double es_energy_between(void* h, int slot, uint64_t t0, uint64_t t1) {
   if (!s || slot < 0 || slot >= int(s->gpus.size())) return NAN;
   std::lock_guard<std::mutex> l(s->mu);
   const auto& g = s->gpus[slot];
-  return s->joules_at(g, t1) - s->joules_at(g, t0);
+  const std::vector<double> u = s->used_times(g);
+  return s->joules_at(g, u, t1) - s->joules_at(g, u, t0);
 }
 
 // Number of counter updates seen for a slot (diagnostics: cadence).
@@ -662,6 +693,26 @@ int es_trace(void* h, int slot, uint64_t* t_out, double* j_out, int max) {
   size_t off = tr.size() - size_t(n);
   for (int i = 0; i < n; ++i) {
     t_out[i] = tr[off + i].host_ns;
+    j_out[i] = tr[off + i].joules;
+  }
+  return n;
+}
+
+// Copy up to max trace points of a slot with everything the window integration sees: when the point was observed
+// (host_ns), the device timestamp that came with it (dev_ns), the host time es_energy_between uses for it
+// (used_ns: the mapped device time or the observation time, see used_times) and the cumulative joules.
+int es_trace_ex(void* h, int slot, uint64_t* host_out, uint64_t* dev_out, double* used_out, double* j_out, int max) {
+  auto* s = static_cast<Sampler*>(h);
+  if (!s || slot < 0 || slot >= int(s->gpus.size())) return -1;
+  std::lock_guard<std::mutex> l(s->mu);
+  const auto& tr = s->gpus[slot].trace;
+  const std::vector<double> u = s->used_times(s->gpus[slot]);
+  int n = std::min<int>(max, int(tr.size()));
+  size_t off = tr.size() - size_t(n);
+  for (int i = 0; i < n; ++i) {
+    host_out[i] = tr[off + i].host_ns;
+    dev_out[i] = tr[off + i].dev_ns;
+    used_out[i] = u[off + i];
     j_out[i] = tr[off + i].joules;
   }
   return n;

@@ -351,7 +351,8 @@ class EnergyMeter:
         with self._lock:
             self._pending = [s for s in self._pending if s["t_ns"] > t1]
         per_gpu = [self.sampler.energy_between(i, t0, t1) for i in range(self.n_gpus)] if "gpu" in self.sources else []
-        gpu_j = float(sum(x for x in per_gpu if not math.isnan(x))) if per_gpu else 0.0
+        # a tracked GPU whose counter could not be read makes the sum NaN, not a finite partial sum that looks whole
+        gpu_j = float(sum(per_gpu)) if per_gpu else 0.0
         if "gpu_idle" in self.sources and self.n_gpus and not math.isnan(self.idle_power_w):
             # the client's board while another process (a co-located remote server) runs on it: charged at the
             # board's measured idle power, what the client device would have drawn waiting on a remote server

@@ -81,6 +81,9 @@ def load() -> ctypes.CDLL:
         lib.es_trace_points.restype = ctypes.c_int64
         lib.es_trace.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
                                  ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+        lib.es_trace_ex.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64),
+                                    ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_double),
+                                    ctypes.POINTER(ctypes.c_double), ctypes.c_int]
         lib.es_trim.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
         lib.es_drain.argtypes = [ctypes.c_void_p, ctypes.POINTER(ESample), ctypes.c_int]
         lib.es_dropped.argtypes = [ctypes.c_void_p]
@@ -156,6 +159,16 @@ class NativeSampler:
         js = (ctypes.c_double * max_points)()
         n = self.lib.es_trace(self.h, slot, ts, js, max_points)
         return [(int(ts[i]), float(js[i])) for i in range(max(n, 0))]
+
+    def trace_ex(self, slot: int, max_points: int = 100000):
+        """Per trace point ``(host_ns, dev_ns, used_ns, joules)``: when it was observed, the device timestamp read
+        with it, the host time ``energy_between`` places it at, and the cumulative joules."""
+        hs = (ctypes.c_uint64 * max_points)()
+        ds = (ctypes.c_uint64 * max_points)()
+        us = (ctypes.c_double * max_points)()
+        js = (ctypes.c_double * max_points)()
+        n = self.lib.es_trace_ex(self.h, slot, hs, ds, us, js, max_points)
+        return [(int(hs[i]), int(ds[i]), float(us[i]), float(js[i])) for i in range(max(n, 0))]
 
     def trim(self, before_ns: int) -> None:
         self.lib.es_trim(self.h, ctypes.c_uint64(before_ns))
