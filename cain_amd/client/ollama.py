@@ -116,8 +116,10 @@ class OllamaClient:
             return False
 
     def generate(self, model: str, prompt: str, stream: bool = False, options: Optional[Dict] = None,
-                 on_chunk=None, system: Optional[str] = None, raw: bool = False) -> GenerateResponse:
-        """``POST /api/generate``; ``system`` / ``raw`` as Ollama's fields (raw: no prompt template)."""
+                 on_chunk=None, system: Optional[str] = None, raw: bool = False,
+                 context: Optional[List[int]] = None) -> GenerateResponse:
+        """``POST /api/generate``; ``system`` / ``raw`` as Ollama's fields (raw: no prompt template); ``context``:
+        the ``context`` of an earlier response, to continue from it."""
         body: Dict[str, Any] = {"model": model, "prompt": prompt, "stream": stream}
         if options:
             body["options"] = options
@@ -125,6 +127,8 @@ class OllamaClient:
             body["system"] = system
         if raw:
             body["raw"] = True
+        if context is not None:
+            body["context"] = [int(t) for t in context]
         return self._post_gen("/api/generate", body, stream, on_chunk)
 
     def chat(self, model: str, messages: List[Dict[str, str]], stream: bool = False,

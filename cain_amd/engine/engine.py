@@ -49,6 +49,13 @@ MAX_ROWS = 256  # rows per forward: decode batch (runtime.hip CAIN_MAX_ROWS)
 PREFILL_ROWS = 128  # prompt tokens per prefill forward
 W8_MAX_ROWS = 64  # few-row fp8 / MXFP4 weight kernels (gemm_w8.hip / gemm_w4.hip): rows per forward without W8A8
 W8A8_MIN_ROWS = 16  # fp8 engines run forwards of more rows on the W8A8 wide kernel (csrc/wgemm8.hip)
+# Prefix reuse (``prefix_cache=True``): a request copies a prefix from another slot (csrc/kv_prefix.hip) instead of
+# reusing a free slot in place only when that saves at least this many prompt tokens of prefill.  Measured on the
+# graph-free admit path (profiles/r11/prefix_cache/README.md; llama3.1:8b and qwen2:1.5b, bf16, one box, interleaved):
+# one copy launch costs 36 - 117 us of wall time (64 .. 2,016 positions), a prefill forward 1.1 / 2.8 ms for its first
+# token and 6.6 / 9.1 us for each further one, so a copy pays for itself from 13 tokens at the longest prefix on the
+# dearer model; 16 covers every row of the table.
+PREFIX_COPY_MIN = 16
 
 
 @dataclass
@@ -62,6 +69,7 @@ class GenResult:
     prompt_eval_duration_ns: int = 0
     eval_duration_ns: int = 0
     total_duration_ns: int = 0
+    prompt_cached: int = 0  # leading prompt tokens whose KV a cache slot already held (prefix reuse)
 
     @property
     def prompt_eval_count(self) -> int:
@@ -71,16 +79,18 @@ class GenResult:
     def eval_count(self) -> int:
         return len(self.tokens)
 
-    def ollama_json(self, created_at: Optional[str] = None) -> Dict:
+    def ollama_json(self, created_at: Optional[str] = None, context: bool = False) -> Dict:
+        """``context``: fill Ollama's ``context`` (the prompt's token ids, then the generated ones: what a client
+        sends back to continue); otherwise it stays empty and the response small."""
         import datetime
 
-        return {
+        d = {
             "model": self.model,
             "created_at": created_at or datetime.datetime.utcnow().isoformat() + "Z",
             "response": self.text,
             "done": True,
             "done_reason": self.done_reason,
-            "context": [],
+            "context": list(self.prompt_tokens) + list(self.tokens) if context else [],
             "total_duration": self.total_duration_ns,
             "load_duration": self.load_duration_ns,
             "prompt_eval_count": self.prompt_eval_count,
@@ -88,6 +98,9 @@ class GenResult:
             "eval_count": self.eval_count,
             "eval_duration": self.eval_duration_ns,
         }
+        if self.prompt_cached > 0:
+            d["prompt_cached_count"] = int(self.prompt_cached)
+        return d
 
 
 def _row_options(opts: Optional[Dict], cfg: ModelConfig, index: int, base_seed: int) -> Dict:
@@ -198,6 +211,75 @@ def _attach_native(weights: ModelWeights, path, cfg: ModelConfig, weight_dtype: 
         weights.native = gguf_q4_native(GGUFFile(path), cfg, _q4_format(weight_dtype), device=device)
 
 
+def common_prefix(a: Sequence[int], b: Sequence[int]) -> int:
+    """Length of the longest common prefix of two token lists."""
+    n = min(len(a), len(b))
+    for i in range(n):
+        if a[i] != b[i]:
+            return i
+    return n
+
+
+def plan_prefix_reuse(records: Sequence[Sequence[int]], free_slots: Sequence[int], live_slots: Sequence[int],
+                      prompts: Sequence[Sequence[int]], copy_min: Optional[int] = None):
+    """Which cache slot each new request takes and how much of its prompt that slot already holds.
+
+    ``records[s]``: the tokens whose KV slot ``s`` holds at positions ``0 .. len - 1`` (for a live row the lower
+    bound known at the last poll); ``free_slots``: the free list in its own order (today's choice is its last
+    element, ``pop()``); ``live_slots``: slots of rows that are decoding.  Returns ``[(slot, n, donor)]`` per request,
+    in order: the request prefills from position ``n`` (0: everything), after positions ``[0, n)`` of ``donor`` were
+    copied to ``slot`` when ``donor`` is not None.  Nothing is modified.
+
+    * ``n`` is a longest common token prefix, at most ``len(prompt) - 1``: the last prompt token is the first decode
+      step's input and always runs.
+    * The free slot with the longest match is reused in place (any ``n >= 1``; among equals the one ``pop()`` would
+      reach first).
+    * A slot that cannot be taken -- live, or free but claimed in place by an earlier request of this call, whose
+      old contents stay put until the prefill that follows the copies -- is a donor when its match is longer than
+      the best free slot's by at least ``copy_min``: the request takes the next free slot in ``pop()`` order and
+      copies.  A slot that is the destination of a copy is never a donor, and the records are the ones from before
+      the call, so requests admitted together never feed each other.
+    * With nothing to reuse the slots are exactly ``free_slots.pop()`` per request."""
+    copy_min = PREFIX_COPY_MIN if copy_min is None else int(copy_min)
+    free = list(free_slots)
+    donors = list(live_slots)  # slots whose contents are readable during this call but cannot be taken
+    out = []
+    for p in prompts:
+        if not free:
+            raise ValueError("more requests than free slots")
+        cap = len(p) - 1
+        best_slot, best_n = None, 0
+        for s in reversed(free):
+            n = min(common_prefix(records[s], p), cap) if records[s] else 0
+            if n > best_n:
+                best_slot, best_n = s, n
+        donor, donor_n = None, 0
+        for s in donors:
+            n = min(common_prefix(records[s], p), cap) if records[s] else 0
+            if n > donor_n:
+                donor, donor_n = s, n
+        if donor is not None and donor_n >= best_n + max(1, copy_min):
+            slot = free.pop()
+            out.append((slot, donor_n, donor))
+        elif best_slot is not None:
+            free.remove(best_slot)
+            donors.append(best_slot)
+            out.append((best_slot, best_n, None))
+        else:
+            slot = free.pop()
+            donors.append(slot)  # (an empty or unrelated record: it can still serve a later request of this call)
+            out.append((slot, 0, None))
+    return out
+
+
+def taken_record(record: Sequence[int], n: int, prompt: Sequence[int]) -> List[int]:
+    """The record of a slot taken with reuse ``n`` for ``prompt``, once its prefill ran: whatever the slot held past
+    position ``n`` is stale and goes, the prompt's tokens ``n .. len - 2`` follow."""
+    if list(record[:n]) != list(prompt[:n]):
+        raise ValueError(f"slot record and prompt differ inside the reused prefix ({n} tokens)")
+    return list(record[:n]) + [int(t) for t in prompt[n:len(prompt) - 1]]
+
+
 class DecodeEngine:
     @classmethod
     def from_pretrained(cls, path: str, device: Union[str, torch.device] = "cuda", name: Optional[str] = None,
@@ -212,7 +294,8 @@ class DecodeEngine:
     def __init__(self, model: Union[str, ModelConfig], device: Union[str, torch.device] = "cuda",
                  max_batch: int = 16, max_context: int = 2048, seed: int = 0, backend: Optional[str] = None,
                  steps_per_graph: int = 8, weights: Optional[ModelWeights] = None, tokenizer=None,
-                 keep_natural: bool = False, weight_dtype: str = "bf16", kv_dtype: str = "bf16", cu_limit: int = 0):
+                 keep_natural: bool = False, weight_dtype: str = "bf16", kv_dtype: str = "bf16", cu_limit: int = 0,
+                 prefix_cache: Optional[bool] = None):
         """``weight_dtype="fp8"``: GEMM weights quantised per row to e4m3 (half the weight bytes per decode step):
         forwards of up to 16 rows run W8A16 (gemm_w8.hip, bf16 activations), wider ones W8A8 (wgemm8.hip: the
         activations quantised per row to e4m3, fp8 MFMA) up to 256 rows; CAIN_W8A8=0 keeps W8A16 only (<= 64
@@ -235,7 +318,12 @@ class DecodeEngine:
         the cache memory; csrc/attention.hip KV8).
         ``cu_limit``: run every kernel on a stream whose hardware queue may use only that many CUs (a multiple of
         8; runtime.hip cain_stream_create_cu_limited) and size the grids for them -- the batch-1 energy lever
-        measured by tools/cu_sweep.py.  0: the whole device."""
+        measured by tools/cu_sweep.py.  0: the whole device.
+        ``prefix_cache``: the continuous batch (HIP backend) keeps a record of the tokens each cache slot holds
+        (``slot_tokens``) and a new request prefills only what differs from the best matching slot
+        (``plan_prefix_reuse``; a prefix held by a slot that is still decoding is copied, csrc/kv_prefix.hip).  Off
+        by default (None: ``CAIN_PREFIX_CACHE=1`` turns it on): without it every admit prefills from position 0 and
+        the caches hold exactly what the requests wrote."""
         self.cfg = get_config(model) if isinstance(model, str) else model
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
@@ -249,6 +337,9 @@ class DecodeEngine:
         self.weight_dtype = weight_dtype
         self.kv_dtype = kv_dtype
         self.cu_limit = int(cu_limit)
+        self.prefix_cache = (os.environ.get("CAIN_PREFIX_CACHE", "0") == "1") if prefix_cache is None \
+            else bool(prefix_cache)
+        self.prefill_rows_total = 0  # rows fed to prefill forwards so far
         if self.cu_limit and (self.cu_limit < 0 or self.cu_limit % 8):
             raise ValueError(f"cu_limit must be a positive multiple of 8 (or 0), got {cu_limit}")
         # W8A8 needs whole 128-deep stages, >= 4 of them, on every GEMM's K (all real configs; not the tiny ones)
@@ -296,6 +387,8 @@ class DecodeEngine:
         self.load_duration_ns = time.perf_counter_ns() - t0
         self._first_call = True
         self.last_ttft_ns = 0
+        # per cache slot: the tokens whose KV the slot holds at positions 0 .. len - 1 (prefix_cache; else unused)
+        self.slot_tokens: List[List[int]] = [[] for _ in range(self.max_batch)]
 
     # ---------------------------------------------------------------- hip setup
     def _init_hip(self) -> None:
@@ -513,9 +606,10 @@ class DecodeEngine:
 
     def generate(self, prompts: Sequence[Union[str, Sequence[int]]], num_predict: Union[int, Sequence[int]] = 128,
                  options: Union[None, Dict, Sequence[Optional[Dict]]] = None, use_graph: bool = True,
-                 on_tokens=None) -> List[GenResult]:
+                 on_tokens=None, context: Optional[Sequence[Optional[Sequence[int]]]] = None) -> List[GenResult]:
         """Generate for a batch of prompts (ids or text).  ``on_tokens(list_per_row)`` streams newly
-        generated ids every ``steps_per_graph`` decode steps (and stops early once every row is done)."""
+        generated ids every ``steps_per_graph`` decode steps (and stops early once every row is done).
+        ``context[i]``: token ids prepended to row i's encoded prompt (Ollama's ``context`` of an earlier answer)."""
         prompts = list(prompts)
         B = len(prompts)
         if B == 0:
@@ -526,9 +620,13 @@ class DecodeEngine:
                 sl = slice(i, i + self.max_batch)
                 nps = num_predict[sl] if not isinstance(num_predict, int) else num_predict
                 ops_ = options[sl] if isinstance(options, (list, tuple)) else options
-                out += self.generate(prompts[sl], nps, ops_, use_graph, on_tokens)
+                out += self.generate(prompts[sl], nps, ops_, use_graph, on_tokens,
+                                     context[sl] if context is not None else None)
             return out
-        ids = [self.encode(p) or [self.cfg.bos_id] for p in prompts]
+        if context is not None and len(context) != B:
+            raise ValueError(f"{len(context)} contexts for {B} prompts")
+        ids = [([int(t) for t in context[i]] if context is not None and context[i] else []) + self.encode(p)
+               or [self.cfg.bos_id] for i, p in enumerate(prompts)]
         nps = [int(num_predict)] * B if isinstance(num_predict, int) else [int(x) for x in num_predict]
         opts = list(options) if isinstance(options, (list, tuple)) else [options] * B
         row_opts = [_row_options(o, self.cfg, i, self.seed) for i, o in enumerate(opts)]
@@ -564,6 +662,7 @@ class DecodeEngine:
 
         dev = self.device
         B = len(ids)
+        self._forget_slots(range(B))
         with torch.cuda.stream(self.stream):
             # ---- prefill: all prompt tokens except the last, in <=prefill_chunk-row chunks
             t0 = time.perf_counter_ns()
@@ -642,6 +741,7 @@ class DecodeEngine:
         if self.backend == "torch":
             return torch.stack([self.ref.forward(torch.tensor([p], device=self.device))[0, -1] for p in ids])
         assert B <= self.max_batch
+        self._forget_slots(range(B))
         with torch.cuda.stream(self.stream):
             self._prefill(ids)
             r = self.rows
@@ -653,14 +753,23 @@ class DecodeEngine:
             self.stream.synchronize()
         return out
 
-    def _prefill(self, ids, slots: Optional[Sequence[int]] = None) -> None:
-        """All prompt tokens but the last through the forward, into KV-cache slot ``slots[b]`` (default b)."""
+    def _forget_slots(self, slots) -> None:
+        """These slots are about to be written outside the continuous batch's bookkeeping: their records die."""
+        for s in slots:
+            self.slot_tokens[s] = []
+
+    def _prefill(self, ids, slots: Optional[Sequence[int]] = None, start: Optional[Sequence[int]] = None) -> None:
+        """All prompt tokens but the last through the forward, into KV-cache slot ``slots[b]`` (default b).
+        ``start[b]``: row b's slot already holds positions ``< start[b]`` of this prompt; tokens
+        ``ids[b][start[b]:-1]`` go in at positions ``start[b] ..`` (default: everything from 0)."""
         flat_tok, flat_pos, flat_slot = [], [], []
         for b, p in enumerate(ids):
-            for j, t in enumerate(p[:-1]):
-                flat_tok.append(t)
+            j0 = 0 if start is None else int(start[b])
+            for j in range(j0, len(p) - 1):
+                flat_tok.append(p[j])
                 flat_pos.append(j)
                 flat_slot.append(b if slots is None else int(slots[b]))
+        self.prefill_rows_total += len(flat_tok)
         pr = self.prefill_rows
         for c in range(0, len(flat_tok), self.prefill_chunk):
             n = min(self.prefill_chunk, len(flat_tok) - c)
@@ -766,6 +875,29 @@ class ContinuousBatch:
         self.emitted: List[int] = []
         self.prompt_tokens: List[List[int]] = []
         self.options: List[Dict] = []
+        self.reused: List[int] = []  # per live row: leading prompt tokens its slot already held at admit
+        # prefix-cache bookkeeping per live row (engine.slot_tokens): steps run since admit, the newest polled
+        # token (its KV is not written yet), done at the last poll, last position already dropped from the record
+        self._steps: List[int] = []
+        self._pending: List[Optional[int]] = []
+        self._done: List[bool] = []
+        self._trimmed: List[bool] = []
+
+    def _row_lists(self):
+        return (self.row_slot, self.emitted, self.prompt_tokens, self.options, self.reused, self._steps,
+                self._pending, self._done, self._trimmed)
+
+    def _trim_idled(self) -> None:
+        """A row that finished keeps stepping with its batch and rewrites its last position with the K / V of its
+        last token (module docstring): once a row known to be done has run further steps, that position no longer
+        holds the token the record names, so the record loses it."""
+        eng = self.eng
+        for i in range(self.n):
+            if self._done[i] and not self._trimmed[i] and self._steps[i] > self.emitted[i]:
+                rec = eng.slot_tokens[self.row_slot[i]]
+                if rec and len(rec) == len(self.prompt_tokens[i]) + self.emitted[i] - 1:
+                    rec.pop()
+                self._trimmed[i] = True
 
     @property
     def capacity(self) -> int:
@@ -789,11 +921,33 @@ class ContinuousBatch:
                 raise ValueError(f"prompt of {len(p)} tokens exceeds the context ({eng.T_max})")
             nps.append(max(1, min(int(n), budget)))
             row_opts.append(_row_options(o, eng.cfg, self.n + i, eng.seed))
-        slots = [self.free_slots.pop() for _ in range(k)]
+        if eng.prefix_cache:
+            self._trim_idled()
+            plan = plan_prefix_reuse(eng.slot_tokens, self.free_slots, self.row_slot, ids, PREFIX_COPY_MIN)
+            slots, start = [s for s, _, _ in plan], [n for _, n, _ in plan]
+            for s in slots:
+                self.free_slots.remove(s)
+            copies = [(d, s, n) for s, n, d in plan if d is not None and n > 0]
+        else:
+            slots, start, copies = [self.free_slots.pop() for _ in range(k)], None, []
         rows = list(range(self.n, self.n + k))
         r = eng.rows
+        # the records the slots have once this call's copies and prefill ran (a copy's destination: the donor's)
+        records = [taken_record(eng.slot_tokens[s if d is None else d], n, p) for (s, n, d), p in zip(plan, ids)] \
+            if eng.prefix_cache else []
+        eng._forget_slots(slots)
         with torch.cuda.stream(eng.stream):
-            eng._prefill(ids, slots)
+            if copies:  # every donor's prefix in one launch, before any prefill of this call writes a slot
+                cfg = eng.cfg
+                _set_cu_budget(eng.lib, eng.cu_limit)
+                try:
+                    rc = ops.kv_copy_prefix(eng.kcache, eng.vtcache, cfg.n_layers, eng.max_batch, cfg.n_kv_heads,
+                                            cfg.head_dim, eng.T_max, copies, stream=eng.stream)
+                finally:
+                    _set_cu_budget(eng.lib, 0)
+                if rc != 0:
+                    raise RuntimeError(f"cain_kv_copy_prefix refused {copies} (rc={rc})")
+            eng._prefill(ids, slots, start)
             sl = slice(self.n, self.n + k)
             r["tok"][sl].copy_(torch.tensor([p[-1] for p in ids], dtype=torch.int32))
             r["pos"][sl].copy_(torch.tensor([len(p) - 1 for p in ids], dtype=torch.int32))
@@ -807,6 +961,14 @@ class ContinuousBatch:
         self.emitted += [0] * k
         self.prompt_tokens += ids
         self.options += row_opts
+        self.reused += list(start) if start is not None else [0] * k
+        self._steps += [0] * k
+        self._pending += [None] * k
+        self._done += [False] * k
+        self._trimmed += [False] * k
+        if eng.prefix_cache:
+            for s, rec in zip(slots, records):
+                eng.slot_tokens[s] = rec
         return rows
 
     def step(self, steps: Optional[int] = None) -> None:
@@ -815,6 +977,8 @@ class ContinuousBatch:
             return
         steps = steps or eng.steps_per_graph
         stream_h = ctypes.c_void_p(eng.stream.cuda_stream)
+        for i in range(self.n):
+            self._steps[i] += steps
         with torch.cuda.stream(eng.stream):
             k = eng.steps_per_graph
             if steps >= k:
@@ -838,10 +1002,22 @@ class ContinuousBatch:
             done = eng.rows["done"][: self.n].cpu().tolist()
             hi = max(ng)
             gen = eng.gen[: self.n, :hi].cpu() if hi else None
-        new = []
+        new, seen = [], list(self.emitted)
         for i in range(self.n):
             new.append(gen[i, self.emitted[i]: ng[i]].tolist() if ng[i] > self.emitted[i] else [])
             self.emitted[i] = ng[i]
+        if eng.prefix_cache:
+            # a row that produced g holds prompt + g[:-1]: each step wrote the KV of the token it consumed
+            for i, fresh in enumerate(new):
+                if fresh:
+                    rec = eng.slot_tokens[self.row_slot[i]]
+                    # (a record cleared behind this batch's back -- a static generate on the engine -- stays cleared)
+                    if len(rec) == len(self.prompt_tokens[i]) - 1 + seen[i]:
+                        rec.append(self.prompt_tokens[i][-1] if self._pending[i] is None else self._pending[i])
+                        rec.extend(fresh[:-1])
+                    self._pending[i] = fresh[-1]
+                self._done[i] = bool(done[i])
+            self._trim_idled()
         return new, [bool(d) for d in done]
 
     def tokens(self, row: int) -> List[int]:
@@ -861,6 +1037,8 @@ class ContinuousBatch:
         movers = [j for j in keep if j >= n_new]
         for h, j in zip(holes, movers):
             moves[j] = h
+        if eng.prefix_cache:
+            self._trim_idled()
         for h in dead:
             self.free_slots.append(self.row_slot[h])
         if moves:
@@ -880,12 +1058,11 @@ class ContinuousBatch:
                 sp = eng.sample_params.view(-1, ops.SAMPLE_BYTES)
                 sp[dst] = sp[src]
             for j, h in moves.items():
-                self.row_slot[h] = self.row_slot[j]
-                self.emitted[h] = self.emitted[j]
-                self.prompt_tokens[h] = self.prompt_tokens[j]
-                self.options[h] = self.options[j]
+                for lst in self._row_lists():
+                    lst[h] = lst[j]
         with torch.cuda.stream(eng.stream):
             eng.rows["slot"][n_new: self.n].fill_(-1)  # vacated rows: skipped by the sampler
         self.n = n_new
-        del self.row_slot[n_new:], self.emitted[n_new:], self.prompt_tokens[n_new:], self.options[n_new:]
+        for lst in self._row_lists():
+            del lst[n_new:]
         return moves

@@ -22,6 +22,7 @@ op                     source                      replaces (Ollama/llama.cpp)
 ``rmsnorm``            csrc/norm.hip               RMSNorm (standalone; the engine fuses it)
 ``embed``              csrc/norm.hip               embedding gather (+Gemma scale)
 ``attention``          csrc/attention.hip          decode / prefill attention (split-K, in-kernel combine)
+``kv_copy_prefix``     csrc/kv_prefix.hip          a slot's cached prompt prefix copied to another slot
 ``sample``             csrc/sample.hip             repeat-penalty/temperature/top-k/top-p
 ``Plan``               csrc/runtime.hip            per-step schedule + hipGraph replay
 =====================  ==========================  =============================
@@ -158,6 +159,7 @@ def load() -> ctypes.CDLL:
         lib.cain_stream_create_cu_limited.restype = vp
         lib.cain_stream_create_cu_limited.argtypes = [ci]
         lib.cain_stream_destroy.argtypes = [vp]
+        lib.cain_kv_copy_prefix.argtypes = [vp, vp, ctypes.c_longlong, ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp]
         if os.environ.get("CAIN_WGEMM_INLINE") and hasattr(real, "cain_wgemm_set_inline"):  # A/B runs
             real.cain_wgemm_set_inline(int(os.environ["CAIN_WGEMM_INLINE"]))
         if os.environ.get("CAIN_SAMPLE_CM"):  # A/B runs (set_sample_cm)
@@ -720,6 +722,41 @@ def kfrag_off(t: int, d: int, hd: int) -> int:
 def vfrag_off(t: int, d: int, hd: int) -> int:
     """Host mirror of common.h vfrag_off."""
     return ((t >> 5) * (hd >> 4) + (d >> 4)) * 512 + ((d & 15) + 16 * ((t & 15) >> 2)) * 8 + 4 * ((t >> 4) & 1) + (t & 3)
+
+
+def kv_copy_prefix(kcache: torch.Tensor, vtcache: torch.Tensor, L: int, S: int, Hkv: int, hd: int, T_max: int,
+                   pairs, stream=None, kv_layer_elems: Optional[int] = None) -> int:
+    """Copy cache positions ``[0, n)`` of slot ``src`` to slot ``dst`` for every ``(src, dst, n)`` of ``pairs``: all
+    layers, both caches, every kv head, one launch (csrc/kv_prefix.hip) on ``stream`` (a torch stream; default the
+    current one).  Returns the entry's code: 0, or -1 when it refused the arguments (nothing launched, the caches
+    untouched) -- callers that cannot go on without the copy raise on it."""
+    lib = load()
+    _gpu(kcache, vtcache)
+    kv8 = is_fp8_cache(kcache)
+    assert kv8 == is_fp8_cache(vtcache)
+    pairs = [tuple(int(x) for x in p) for p in pairs]
+    n = len(pairs)
+    arr = lambda k: (ci * max(n, 1))(*[p[k] for p in pairs])  # noqa: E731
+    elems = int(kv_layer_elems) if kv_layer_elems is not None else S * Hkv * T_max * hd
+    st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    return int(lib.cain_kv_copy_prefix(_p(kcache), _p(vtcache), elems, L, S, Hkv, hd, T_max, int(kv8),
+                                       arr(0), arr(1), arr(2), n, st))
+
+
+def kv_copy_prefix_ref(kcache: torch.Tensor, vtcache: torch.Tensor, L: int, S: int, Hkv: int, hd: int, T_max: int,
+                       pairs) -> None:
+    """The same copy on CPU tensors, in place, from the definition: both caches unpacked to natural
+    ``[layer, slot, kv head, position, head dim]``, positions ``< n`` of ``dst`` assigned from ``src`` one by one,
+    and packed again (no byte ranges, no offset arithmetic of the kernel's)."""
+    k = unpack_kcache(kcache.view(L, S, Hkv, T_max, hd)).clone()
+    v = unpack_vcache(vtcache.view(L, S, Hkv, hd, T_max)).clone()
+    k0, v0 = k.clone(), v.clone()  # every pair reads the caches as they were
+    for src, dst, n in pairs:
+        for t in range(int(n)):
+            k[:, dst, :, t] = k0[:, src, :, t]
+            v[:, dst, :, t] = v0[:, src, :, t]
+    kcache.copy_(pack_kcache(k).reshape(kcache.shape))
+    vtcache.copy_(pack_vcache(v).reshape(vtcache.shape))
 
 
 def attention_ml_floats(M: int, H: int, Hkv: int, nsplit: int) -> int:

@@ -158,7 +158,7 @@ COMMANDS = {
     "config-create": ("[path_to_user_specified_dir]", cmd_config_create),
     "prepare": ("", cmd_prepare),
     "analyze": ("<run_table.csv> [--out DIR]", cmd_analyze),
-    "serve": ("[--host H] [--port P] [--models m1,m2] [--device N]", cmd_serve),
+    "serve": ("[--host H] [--port P] [--models m1,m2] [--device N] [--prefix-cache]", cmd_serve),
     "generate": ("--model M --prompt P [--num-predict N] [--checkpoint PATH]", cmd_generate),
     "convert": ("<checkpoint dir | .gguf> <out.gguf> [--type F16|Q8_0|Q4_0|Q4_K|Q6_K|Q4_K_M|...]", cmd_convert),
     "help": ("", cmd_help),

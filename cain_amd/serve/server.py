@@ -25,6 +25,13 @@ rather than the whole earlier batch.  Other backends (torch oracle, fake) and
 ``batch_window_ms`` into one batch and run it to completion (trial batching on
 the server side).
 
+Prefix reuse: ``/api/generate`` takes Ollama's ``context`` (token ids of an earlier answer, prepended to the new
+prompt's tokens) at all times and returns one when asked to (a request that sent one, or ``--prefix-cache``).  With
+``--prefix-cache`` the continuous batch keeps each cache slot's tokens and a request prefills only what differs from
+the best matching slot (engine.plan_prefix_reuse): a chat's next turn, or requests behind one system prompt, skip
+the shared prefix; the final JSON then carries ``prompt_cached_count``.  Off by default: responses keep their size
+and every request computes its whole prompt, as the study's measurements assume.
+
 Tracing: started with ``--trace-dir DIR``, the engine backend records every decode batch
 with ``torch.profiler`` (host ops + GPU kernels) and writes a Chrome trace to DIR; the response JSON
 names it in ``cain_trace`` so the client can file it with its run (the study moves it into run_dir).
@@ -77,6 +84,8 @@ class Job:
     error: Optional[BaseException] = None
     t_submit: float = field(default_factory=time.perf_counter)
     trace_file: Optional[str] = None  # Chrome trace of the batch that decoded this job (--trace-dir)
+    context: Optional[List[int]] = None  # token ids that go in front of the prompt's (Ollama's ``context``)
+    want_context: bool = False       # the response carries ``context``
 
 
 class Backend:
@@ -102,6 +111,12 @@ class Backend:
 
     def model_info(self, model: str) -> Dict[str, Any]:
         return {}
+
+    def vocab_size(self, model: str) -> Optional[int]:
+        """Token ids a request's ``context`` may hold are below this (None: not checked)."""
+        return None
+
+    prefix_cache = False
 
 
 # Ollama's quantization_level names for the engine's weight storage
@@ -136,8 +151,9 @@ class EngineBackend(Backend):
     def __init__(self, models: List[str], device: str = "cuda:0", max_batch: int = 16, max_context: int = 2048,
                  backend: Optional[str] = None, seed: int = 0, preload: bool = False, steps_per_graph: int = 8,
                  trace_dir: Optional[str] = None, weight_dtype: str = "bf16", continuous: bool = True,
-                 kv_dtype: str = "bf16"):
+                 kv_dtype: str = "bf16", prefix_cache: bool = False):
         self._models = list(models)
+        self.prefix_cache = bool(prefix_cache)
         self.kv_dtype = kv_dtype
         # continuous batching needs the HIP engine; tracing records whole static batches
         self.continuous = continuous and not trace_dir
@@ -173,7 +189,7 @@ class EngineBackend(Backend):
                 eng = DecodeEngine(model, device=self.device, max_batch=self._max_batch,
                                    max_context=self.max_context, backend=self.backend, seed=self.seed,
                                    steps_per_graph=self.steps_per_graph, weight_dtype=self.weight_dtype,
-                                   kv_dtype=self.kv_dtype)
+                                   kv_dtype=self.kv_dtype, prefix_cache=self.prefix_cache)
                 self.engines[model] = eng
             return eng
 
@@ -194,6 +210,11 @@ class EngineBackend(Backend):
             msgs = ([{"role": "system", "content": body["system"]}] if body.get("system") else []) + \
                    [{"role": "user", "content": body.get("prompt", "")}]
         return tok.encode(tok.render_chat(msgs), add_bos=False)
+
+    def vocab_size(self, model: str) -> Optional[int]:
+        from ..models import get_config
+
+        return int(get_config(model).vocab) if model in self._models else None
 
     def model_info(self, model: str) -> Dict[str, Any]:
         from ..models import get_config
@@ -232,7 +253,8 @@ class EngineBackend(Backend):
 
         def gen():
             return eng.generate([j.prompt for j in jobs], [j.num_predict for j in jobs], [j.options for j in jobs],
-                                on_tokens=on_tokens if any(streams) else None)
+                                on_tokens=on_tokens if any(streams) else None,
+                                context=[j.context for j in jobs] if any(j.context for j in jobs) else None)
 
         if self.trace_dir:
             res, path = self._traced(model, gen)
@@ -295,7 +317,7 @@ class EngineBackend(Backend):
         ids: List[List[int]] = []
         for j in pending:
             try:
-                p = eng.encode(j.prompt) or [eng.cfg.bos_id]
+                p = list(j.context or []) + eng.encode(j.prompt) or [eng.cfg.bos_id]
                 if len(p) >= eng.T_max:
                     raise ValueError(f"prompt of {len(p)} tokens exceeds the context ({eng.T_max})")
             except Exception as exc:  # noqa: BLE001 - reported to this request only
@@ -334,7 +356,7 @@ class EngineBackend(Backend):
             j.result = GenResult(model, list(cb.prompt_tokens[r]), toks, tok.decode(toks), reason,
                                  load_duration_ns=0, prompt_eval_duration_ns=int(st["t_pre"] - st["t0"]),
                                  eval_duration_ns=int(now - st["t_pre"]),
-                                 total_duration_ns=int(now - j.t_submit * 1e9))
+                                 total_duration_ns=int(now - j.t_submit * 1e9), prompt_cached=int(cb.reused[r]))
             j.ttft_ns = int(st["t_first"] - st["t0"])
             j.done.set()
         if done_rows:
@@ -468,7 +490,7 @@ class Scheduler:
 
 def _result_json(job: Job, created: Optional[str] = None) -> Dict[str, Any]:
     r = job.result
-    d = r.ollama_json(created or _now())
+    d = r.ollama_json(created or _now(), context=job.want_context)
     d["cain_ttft_ns"] = int(getattr(job, "ttft_ns", 0))
     if job.trace_file:
         d["cain_trace"] = job.trace_file
@@ -516,8 +538,9 @@ class OllamaHandler(BaseHTTPRequestHandler):
             self._send_json(200, {"models": [{"name": m, "model": m, "modified_at": _now(), "size": 0,
                                               "details": be.model_info(m).get("details", {})} for m in be.models()]})
         elif self.path == "/api/ps":
-            self._send_json(200, {"models": [{"name": m, "model": m,
-                                              "expires_at": "2999-01-01T00:00:00Z"}
+            be = self.scheduler.backend
+            self._send_json(200, {"models": [{"name": m, "model": m, "expires_at": "2999-01-01T00:00:00Z",
+                                              "prefix_cache": bool(getattr(be, "prefix_cache", False))}
                                              for m in self.scheduler.queues]})
         else:
             self._send_json(404, {"error": "not found"})
@@ -557,6 +580,14 @@ class OllamaHandler(BaseHTTPRequestHandler):
             return self._send_json(404, {"error": str(exc).strip("'\"")})
         except Exception as exc:  # noqa: BLE001 - a template that fails to render, a model that fails to load
             return self._send_json(400, {"error": f"{type(exc).__name__}: {exc}"})
+        context = None
+        if not chat and body.get("context") is not None:
+            context = body["context"]
+            vocab = self.scheduler.backend.vocab_size(model)
+            if not isinstance(context, list) or any(isinstance(t, bool) or not isinstance(t, int) for t in context):
+                return self._send_json(400, {"error": "context must be a list of token ids"})
+            if any(t < 0 or (vocab is not None and t >= vocab) for t in context):
+                return self._send_json(400, {"error": f"context holds a token id outside the vocabulary ({vocab})"})
         opts = dict(body.get("options") or {})
         n = opts.get("num_predict")
         # the length policy reads the user's words ("In N words ..."), not the template around them
@@ -564,7 +595,9 @@ class OllamaHandler(BaseHTTPRequestHandler):
         stream = body.get("stream", True)
         created = _now()
         chunks: "queue.Queue[str]" = queue.Queue()
-        job = Job(model, prompt, num_predict, opts, stream=chunks.put if stream else None)
+        job = Job(model, prompt, num_predict, opts, stream=chunks.put if stream else None, context=context,
+                  want_context=not chat and (context is not None or bool(getattr(self.scheduler.backend,
+                                                                                "prefix_cache", False))))
         try:
             self.scheduler.submit(job)
         except KeyError as exc:
@@ -666,6 +699,9 @@ def main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--static-batching", action="store_true",
                     help="batch requests that arrive within --batch-window-ms and run each batch to completion "
                          "(default on the HIP engine: continuous batching)")
+    ap.add_argument("--prefix-cache", action="store_true",
+                    help="keep each cache slot's tokens between requests and prefill only what differs from the best "
+                         "matching slot (continuous batching on the HIP engine); responses carry 'context'")
     ap.add_argument("--checkpoint", action="append", metavar="TAG=PATH",
                     help="serve a Hugging Face checkpoint directory or GGUF file under TAG (repeatable; models/hf.py); "
                          "PATH 'ollama' takes the blob a local Ollama store keeps for TAG")
@@ -682,7 +718,7 @@ def main(argv: Optional[List[str]] = None) -> None:
     else:
         be = EngineBackend(models, device=ns.device, max_batch=ns.max_batch, max_context=ns.max_context,
                            backend=ns.backend, preload=ns.preload, trace_dir=ns.trace_dir, weight_dtype=ns.weights,
-                           continuous=not ns.static_batching, kv_dtype=ns.kv)
+                           continuous=not ns.static_batching, kv_dtype=ns.kv, prefix_cache=ns.prefix_cache)
     srv = make_server(be, ns.host, ns.port, ns.batch_window_ms, ns.verbose)
     print(f"[serve] Ollama-compatible API on http://{ns.host}:{srv.server_address[1]} models={models}", flush=True)
     try:
