@@ -46,6 +46,11 @@ class GenerateResponse:
     def prompt_eval_count(self) -> int:
         return int(self.data.get("prompt_eval_count", 0) or 0)
 
+    @property
+    def logprobs(self) -> Optional[List[Dict[str, Any]]]:
+        """The ``logprobs`` entries of a request that asked for them (one per generated token), else None."""
+        return self.data.get("logprobs")
+
     def stats(self) -> Dict[str, Any]:
         d = self.data
         ns = 1e-9
@@ -70,6 +75,13 @@ class GenerateResponse:
 
 class OllamaError(RuntimeError):
     pass
+
+
+def _lp_fields(body: Dict[str, Any], logprobs: bool, top_logprobs: int) -> None:
+    if logprobs:
+        body["logprobs"] = True
+    if top_logprobs:
+        body["top_logprobs"] = int(top_logprobs)
 
 
 def _split(url: str):
@@ -117,9 +129,11 @@ class OllamaClient:
 
     def generate(self, model: str, prompt: str, stream: bool = False, options: Optional[Dict] = None,
                  on_chunk=None, system: Optional[str] = None, raw: bool = False,
-                 context: Optional[List[int]] = None) -> GenerateResponse:
+                 context: Optional[List[int]] = None, logprobs: bool = False,
+                 top_logprobs: int = 0) -> GenerateResponse:
         """``POST /api/generate``; ``system`` / ``raw`` as Ollama's fields (raw: no prompt template); ``context``:
-        the ``context`` of an earlier response, to continue from it."""
+        the ``context`` of an earlier response, to continue from it; ``logprobs`` / ``top_logprobs``: the response's
+        ``logprobs`` list (``GenerateResponse.logprobs``; streamed pieces' entries concatenated)."""
         body: Dict[str, Any] = {"model": model, "prompt": prompt, "stream": stream}
         if options:
             body["options"] = options
@@ -129,13 +143,15 @@ class OllamaClient:
             body["raw"] = True
         if context is not None:
             body["context"] = [int(t) for t in context]
+        _lp_fields(body, logprobs, top_logprobs)
         return self._post_gen("/api/generate", body, stream, on_chunk)
 
     def chat(self, model: str, messages: List[Dict[str, str]], stream: bool = False,
-             options: Optional[Dict] = None) -> GenerateResponse:
+             options: Optional[Dict] = None, logprobs: bool = False, top_logprobs: int = 0) -> GenerateResponse:
         body: Dict[str, Any] = {"model": model, "messages": messages, "stream": stream}
         if options:
             body["options"] = options
+        _lp_fields(body, logprobs, top_logprobs)
         return self._post_gen("/api/chat", body, stream, None)
 
     def _post_gen(self, path: str, body: Dict, stream: bool, on_chunk) -> GenerateResponse:
@@ -149,6 +165,7 @@ class OllamaClient:
                 data = json.loads(r.read())
                 return GenerateResponse(data, time.perf_counter() - t0)
             ttft = None
+            entries: Optional[List[Dict[str, Any]]] = None
             pieces: List[str] = []
             last: Dict[str, Any] = {}
             n = 0
@@ -158,6 +175,8 @@ class OllamaClient:
                 if "error" in obj:
                     raise OllamaError(obj["error"])
                 piece = obj.get("response", obj.get("message", {}).get("content", ""))
+                if "logprobs" in obj:
+                    entries = (entries or []) + list(obj["logprobs"] or [])
                 if piece and ttft is None:
                     ttft = time.perf_counter() - t0
                 if piece:
@@ -170,6 +189,8 @@ class OllamaClient:
                 final["message"] = {"role": "assistant", "content": "".join(pieces)}
             else:
                 final["response"] = "".join(pieces)
+            if entries is not None:
+                final["logprobs"] = entries
             return GenerateResponse(final, time.perf_counter() - t0, ttft, n)
         finally:
             c.close()

@@ -1,2 +1,2 @@
 """Decode engine (on-device arm)."""
-from .engine import OLLAMA_DEFAULTS, DecodeEngine, GenResult  # noqa: F401
+from .engine import OLLAMA_DEFAULTS, DecodeEngine, GenResult, ScoreResult, logprob_host  # noqa: F401

@@ -70,6 +70,11 @@ class GenResult:
     eval_duration_ns: int = 0
     total_duration_ns: int = 0
     prompt_cached: int = 0  # leading prompt tokens whose KV a cache slot already held (prefix reuse)
+    # per generated token (None: not asked for): its natural-log softmax under the model's own logits (temperature 1,
+    # before the repeat penalty and top-k / top-p), and the ``top_logprobs`` most likely (id, logprob) pairs of that
+    # distribution, logit descending, index ascending on ties
+    logprobs: Optional[List[float]] = None
+    top_logprobs: Optional[List[List[tuple]]] = None
 
     @property
     def prompt_eval_count(self) -> int:
@@ -156,6 +161,62 @@ class _CainPlanDesc(ctypes.Structure):
 class _CainRows(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in ("tok", "pos", "slot", "n_gen", "max_new", "done", "hist", "gen")]
                 + [("ldg", ctypes.c_int), ("sample_params", ctypes.c_void_p)])
+
+
+class _CainLogprob(ctypes.Structure):  # runtime.hip CainLogprob
+    _fields_ = [("topn", ctypes.c_void_p), ("nmax", ctypes.c_int), ("lp", ctypes.c_void_p),
+                ("top_id", ctypes.c_void_p), ("top_lp", ctypes.c_void_p), ("keep", ctypes.c_void_p),
+                ("target", ctypes.c_void_p)]
+
+
+TOP_LOGPROBS_MAX = 20  # Ollama's limit; the entries per token of the device buffers (csrc/logprob.hip LP_TOP)
+
+
+@dataclass
+class ScoreResult:
+    """``DecodeEngine.score`` of one prompt: ``logprobs[j]`` is the logprob of ``tokens[j + 1]`` given
+    ``tokens[:j + 1]`` (n - 1 values for n tokens), ``top_logprobs[j]`` the alternatives at that position."""
+    tokens: List[int]
+    logprobs: List[float]
+    top_logprobs: List[List[tuple]]
+
+    @property
+    def nll(self) -> float:
+        return -float(sum(self.logprobs))
+
+
+def logprob_host(logits: torch.Tensor, n: int = 0):
+    """The definition on the host: float64 log-softmax of one row of fp32 logits; returns it ([V] float64 numpy) with
+    the ``n`` most likely ``(id, logprob)`` pairs, logit descending and index ascending on ties (the samplers'
+    order).  The torch backend's logprobs, and the reference of the device kernels' tests."""
+    lg = logits.detach().to(torch.float32).cpu().numpy()
+    x = lg.astype(np.float64)
+    mx = x.max()
+    ls = x - (mx + np.log(np.exp(x - mx).sum()))
+    V = lg.shape[0]
+    k = min(int(n), V)
+    if k <= 0:
+        return ls, []
+    cand = np.flatnonzero(lg >= np.partition(lg, V - k)[V - k])  # ties with the k-th largest included
+    ids = cand[np.lexsort((cand, -x[cand]))][:k]
+    return ls, [(int(i), float(ls[i])) for i in ids]
+
+
+def _want_logprobs(logprobs, top_logprobs, B: int) -> List[int]:
+    """Per row: -1 (no logprobs) or the number of alternatives, from scalars or per-row sequences."""
+    lps = list(logprobs) if isinstance(logprobs, (list, tuple)) else [logprobs] * B
+    tops = list(top_logprobs) if isinstance(top_logprobs, (list, tuple)) else [top_logprobs] * B
+    if len(lps) != B or len(tops) != B:
+        raise ValueError(f"logprobs / top_logprobs for {len(lps)} / {len(tops)} rows, {B} prompts")
+    out = []
+    for want, n in zip(lps, tops):
+        n = int(n or 0)
+        if not 0 <= n <= TOP_LOGPROBS_MAX:
+            raise ValueError(f"top_logprobs must be in 0..{TOP_LOGPROBS_MAX}, got {n}")
+        if n and not want:
+            raise ValueError("top_logprobs needs logprobs")
+        out.append(n if want else -1)
+    return out
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -476,6 +537,7 @@ class DecodeEngine:
         d.q4_gain = int(bool(packed.get("q4_gain")))  # GGUF blocks as stored: gains applied to the activations
         d.flm_head = MFMT[packed["flm_head"]] if "flm_head" in packed else 0
         self._desc = d
+        self._lp: Optional[Dict[str, torch.Tensor]] = None  # logprob buffers, allocated at first use (_lp_bufs)
         self._plans: Dict[int, int] = {}
         self._graphs: Dict[tuple, int] = {}
         self._cu_stream = None
@@ -547,21 +609,56 @@ class DecodeEngine:
             r.sample_params = _ptr(self.sample_params)
         return r
 
-    def _forward(self, M: int, rows, want_logits: bool, want_sample: bool) -> None:
+    def _lp_bufs(self) -> Dict[str, torch.Tensor]:
+        """Device buffers of the token log-probabilities (csrc/logprob.hip), made when a request first asks: per row
+        ``topn`` (-1: not wanted; ``s_topn``: of ``score``'s rows), rings indexed like ``gen`` (``lp [R, T]``, ``top_id / top_lp [R, T, 20]``), the
+        scratch between the two launches of a decode step, and the per-row targets and results of ``score``."""
+        if self._lp is None:
+            from .. import ops
+
+            dev, R, T, K = self.device, self.gen.shape[0], self.T_max, TOP_LOGPROBS_MAX
+            z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)  # noqa: E731
+            self._lp = dict(topn=torch.full((R,), -1, device=dev, dtype=torch.int32), lp=z(R, T),
+                            top_id=z(R, T, K, dt=torch.int32), top_lp=z(R, T, K), keep=ops.logprob_keep(R, dev),
+                            target=z(R, dt=torch.int32), s_lp=z(R),
+                            s_topn=torch.full((R,), -1, device=dev, dtype=torch.int32), s_top_id=z(R, K, dt=torch.int32),
+                            s_top_lp=z(R, K))
+        return self._lp
+
+    def _lp_struct(self, decode: bool, nmax: int = TOP_LOGPROBS_MAX) -> _CainLogprob:
+        b = self._lp_bufs()
+        q = _CainLogprob()
+        q.topn, q.nmax = _ptr(b["topn" if decode else "s_topn"]), int(nmax)
+        if decode:
+            assert b["lp"].stride(0) == self.gen.stride(0)
+            q.lp, q.top_id, q.top_lp, q.keep = _ptr(b["lp"]), _ptr(b["top_id"]), _ptr(b["top_lp"]), _ptr(b["keep"])
+        else:
+            q.lp, q.top_id, q.top_lp, q.target = (_ptr(b["s_lp"]), _ptr(b["s_top_id"]), _ptr(b["s_top_lp"]),
+                                                  _ptr(b["target"]))
+        return q
+
+    def _forward(self, M: int, rows, want_logits: bool, want_sample: bool, lp: Optional[_CainLogprob] = None) -> None:
         rs = self._rows_struct(rows, want_sample)
         plan = self._plan(M)
         _set_cu_budget(self.lib, self.cu_limit)  # launch sizing for this engine's stream (0: whole device)
         try:
-            rc = self.lib.cain_plan_forward(ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits),
-                                            int(want_sample), ctypes.c_void_p(self.stream.cuda_stream))
+            if lp is not None:
+                rc = self.lib.cain_plan_forward_lp(ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits),
+                                                   int(want_sample), ctypes.byref(lp),
+                                                   ctypes.c_void_p(self.stream.cuda_stream))
+            else:
+                rc = self.lib.cain_plan_forward(ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits),
+                                                int(want_sample), ctypes.c_void_p(self.stream.cuda_stream))
         finally:
             _set_cu_budget(self.lib, 0)
         if rc != 0:
             where = self.lib.cain_plan_last_failure()
             raise RuntimeError(f"cain_plan_forward failed rc={rc}" + (f" at {where.decode()}" if where else ""))
 
-    def _graph(self, M: int, steps: int) -> int:
-        key = (M, steps)
+    def _graph(self, M: int, steps: int, lp: bool = False) -> int:
+        """``lp``: the steps also compute token log-probabilities (for the rows whose ``topn`` says so when the graph
+        runs) -- a cache entry of its own; without it the graph is launch for launch the one it always was."""
+        key = (M, steps, "lp") if lp else (M, steps)
         g = self._graphs.get(key)
         if g is None:
             rs = self._rows_struct(self.rows, True)
@@ -569,8 +666,14 @@ class DecodeEngine:
             plan = self._plan(M)
             _set_cu_budget(self.lib, self.cu_limit)
             try:
-                g = self.lib.cain_plan_capture(ctypes.c_void_p(plan), M, ctypes.byref(rs), steps,
-                                               ctypes.c_void_p(self.stream.cuda_stream), ctypes.byref(err))
+                if lp:
+                    q = self._lp_struct(True)
+                    g = self.lib.cain_plan_capture_lp(ctypes.c_void_p(plan), M, ctypes.byref(rs), steps,
+                                                      ctypes.byref(q), ctypes.c_void_p(self.stream.cuda_stream),
+                                                      ctypes.byref(err))
+                else:
+                    g = self.lib.cain_plan_capture(ctypes.c_void_p(plan), M, ctypes.byref(rs), steps,
+                                                   ctypes.c_void_p(self.stream.cuda_stream), ctypes.byref(err))
             finally:
                 _set_cu_budget(self.lib, 0)
             if not g:
@@ -606,14 +709,23 @@ class DecodeEngine:
 
     def generate(self, prompts: Sequence[Union[str, Sequence[int]]], num_predict: Union[int, Sequence[int]] = 128,
                  options: Union[None, Dict, Sequence[Optional[Dict]]] = None, use_graph: bool = True,
-                 on_tokens=None, context: Optional[Sequence[Optional[Sequence[int]]]] = None) -> List[GenResult]:
+                 on_tokens=None, context: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                 logprobs: Union[bool, Sequence[bool]] = False,
+                 top_logprobs: Union[int, Sequence[int]] = 0) -> List[GenResult]:
         """Generate for a batch of prompts (ids or text).  ``on_tokens(list_per_row)`` streams newly
         generated ids every ``steps_per_graph`` decode steps (and stops early once every row is done).
-        ``context[i]``: token ids prepended to row i's encoded prompt (Ollama's ``context`` of an earlier answer)."""
+        ``context[i]``: token ids prepended to row i's encoded prompt (Ollama's ``context`` of an earlier answer).
+        ``logprobs`` (one flag or one per row): each result carries the log-probability of every generated token --
+        the natural-log softmax of the model's own logits, temperature 1, before the repeat penalty and top-k /
+        top-p -- and the ``top_logprobs`` (0 .. 20) most likely ``(id, logprob)`` of that distribution per token,
+        logit descending, index ascending on ties.  On the HIP backend both are computed on the device inside the
+        decode graphs (csrc/logprob.hip); the tokens are the same with and without.  With logprobs asked for,
+        ``on_tokens`` gets a second argument: per row ``(logprobs, top_logprobs)`` of the new tokens, or None."""
         prompts = list(prompts)
         B = len(prompts)
         if B == 0:
             return []
+        want = _want_logprobs(logprobs, top_logprobs, B)
         if B > self.max_batch:
             out = []
             for i in range(0, B, self.max_batch):
@@ -621,7 +733,8 @@ class DecodeEngine:
                 nps = num_predict[sl] if not isinstance(num_predict, int) else num_predict
                 ops_ = options[sl] if isinstance(options, (list, tuple)) else options
                 out += self.generate(prompts[sl], nps, ops_, use_graph, on_tokens,
-                                     context[sl] if context is not None else None)
+                                     context[sl] if context is not None else None,
+                                     [w >= 0 for w in want[sl]], [max(w, 0) for w in want[sl]])
             return out
         if context is not None and len(context) != B:
             raise ValueError(f"{len(context)} contexts for {B} prompts")
@@ -636,12 +749,13 @@ class DecodeEngine:
                 raise ValueError(f"prompt of {len(ids[i])} tokens exceeds the context ({self.T_max})")
             nps[i] = max(1, min(nps[i], budget))
         t0 = time.perf_counter_ns()
+        lps = None  # per row (logprobs, top_logprobs) or None
         if self.backend == "torch":
-            gen, t_pref, t_dec = self._generate_torch(ids, nps, row_opts)
+            gen, t_pref, t_dec, lps = self._generate_torch(ids, nps, row_opts, want)
             if on_tokens is not None:
-                on_tokens(gen)
+                on_tokens(gen, lps) if lps is not None else on_tokens(gen)
         else:
-            gen, t_pref, t_dec = self._generate_hip(ids, nps, row_opts, use_graph, on_tokens)
+            gen, t_pref, t_dec, lps = self._generate_hip(ids, nps, row_opts, use_graph, on_tokens, want=want)
         total = time.perf_counter_ns() - t0
         load = self.load_duration_ns if self._first_call else 0
         self._first_call = False
@@ -655,13 +769,27 @@ class DecodeEngine:
                                  load_duration_ns=load, prompt_eval_duration_ns=t_pref,
                                  eval_duration_ns=int(t_dec * len(toks) / max(1, steps)),
                                  total_duration_ns=total + load))
+            if lps is not None and lps[i] is not None:
+                out[-1].logprobs, out[-1].top_logprobs = lps[i]
         return out
 
-    def _generate_hip(self, ids, nps, row_opts, use_graph, on_tokens=None, check_every: int = 1):
+    def _read_logprobs(self, row: int, lo: int, hi: int, n: int):
+        """(logprobs, top_logprobs) of tokens ``lo .. hi - 1`` of decode row ``row`` from the device rings."""
+        b = self._lp_bufs()
+        if hi <= lo:
+            return [], []
+        lp = b["lp"][row, lo:hi].cpu().tolist()
+        if n <= 0:
+            return lp, [[] for _ in lp]
+        ti, tl = b["top_id"][row, lo:hi, :n].cpu().tolist(), b["top_lp"][row, lo:hi, :n].cpu().tolist()
+        return lp, [list(zip(a, c)) for a, c in zip(ti, tl)]
+
+    def _generate_hip(self, ids, nps, row_opts, use_graph, on_tokens=None, check_every: int = 1, want=None):
         from .. import ops
 
         dev = self.device
         B = len(ids)
+        with_lp = want is not None and any(w >= 0 for w in want)
         self._forget_slots(range(B))
         with torch.cuda.stream(self.stream):
             # ---- prefill: all prompt tokens except the last, in <=prefill_chunk-row chunks
@@ -676,6 +804,10 @@ class DecodeEngine:
             r["done"][:B].zero_()
             r["max_new"][:B].copy_(torch.tensor(nps, dtype=torch.int32))
             self.sample_params[: ops.SAMPLE_BYTES * B].copy_(ops.sample_params_tensor(row_opts, "cpu").to(dev))
+            lq = None
+            if with_lp:
+                self._lp_bufs()["topn"][:B].copy_(torch.tensor(want, dtype=torch.int32))
+                lq = self._lp_struct(True, max(want))
             self.stream.synchronize()
             t1 = time.perf_counter_ns()
             steps = max(nps)
@@ -684,16 +816,19 @@ class DecodeEngine:
             def launch(nsteps: int) -> None:
                 if not use_graph:
                     for _ in range(nsteps):
-                        self._forward(B, r, want_logits=True, want_sample=True)
+                        if lq is None:  # (the call it always was: wrappers of _forward see the same arguments)
+                            self._forward(B, r, want_logits=True, want_sample=True)
+                        else:
+                            self._forward(B, r, want_logits=True, want_sample=True, lp=lq)
                     return
                 k = self.steps_per_graph
-                g = self._graph(B, k) if nsteps >= k else None
+                g = self._graph(B, k, with_lp) if nsteps >= k else None
                 for _ in range(nsteps // k):
                     rc = self.lib.cain_graph_launch(ctypes.c_void_p(g), stream_h)
                     if rc != 0:
                         raise RuntimeError(f"hipGraphLaunch failed rc={rc}")
                 if nsteps % k:
-                    g1 = self._graph(B, 1)
+                    g1 = self._graph(B, 1, with_lp)
                     for _ in range(nsteps % k):
                         if self.lib.cain_graph_launch(ctypes.c_void_p(g1), stream_h) != 0:
                             raise RuntimeError("hipGraphLaunch failed")
@@ -707,14 +842,20 @@ class DecodeEngine:
             watch = on_tokens is not None or any(o["eos_id"] >= 0 or o["stop"] for o in row_opts)
             chunk = self.steps_per_graph * max(1, int(check_every))
 
+            def emit(new, ng) -> None:
+                if with_lp:
+                    on_tokens(new, [self._read_logprobs(i, emitted[i], ng[i], want[i]) if want[i] >= 0 else None
+                                    for i in range(B)])
+                else:
+                    on_tokens(new)
+                for i in range(B):
+                    emitted[i] = ng[i]
+
             def poll() -> bool:
                 ng = r["n_gen"][:B].cpu().tolist()
                 if on_tokens is not None:
-                    new = [self.gen[i, emitted[i]: ng[i]].cpu().tolist() if ng[i] > emitted[i] else []
-                           for i in range(B)]
-                    for i in range(B):
-                        emitted[i] = ng[i]
-                    on_tokens(new)
+                    emit([self.gen[i, emitted[i]: ng[i]].cpu().tolist() if ng[i] > emitted[i] else []
+                          for i in range(B)], ng)
                 return bool(r["done"][:B].all())
 
             if watch and poll():
@@ -728,10 +869,12 @@ class DecodeEngine:
             n_gen = r["n_gen"][:B].cpu().tolist()
             gen = self.gen[:B].cpu()
             if on_tokens is not None:
-                on_tokens([gen[i, emitted[i]: n_gen[i]].tolist() for i in range(B)])
+                emit([gen[i, emitted[i]: n_gen[i]].tolist() for i in range(B)], n_gen)
+            lps = [self._read_logprobs(i, 0, n_gen[i], want[i]) if want[i] >= 0 else None
+                   for i in range(B)] if with_lp else None
             t2 = time.perf_counter_ns()
         self.last_ttft_ns = t_first - t0
-        return [gen[i, : n_gen[i]].tolist() for i in range(B)], t1 - t0, t2 - t1
+        return [gen[i, : n_gen[i]].tolist() for i in range(B)], t1 - t0, t2 - t1, lps
 
     @torch.no_grad()
     def last_logits(self, prompts: Sequence[Union[str, Sequence[int]]]) -> torch.Tensor:
@@ -753,22 +896,66 @@ class DecodeEngine:
             self.stream.synchronize()
         return out
 
+    @torch.no_grad()
+    def score(self, prompts: Sequence[Union[str, Sequence[int]]], top_logprobs: int = 0) -> List[ScoreResult]:
+        """Teacher-forced log-probabilities: for each prompt (ids or text) of n tokens the logprob of tokens
+        1 .. n - 1, token j scored by the logits at position j - 1 (same definition as ``generate(logprobs=True)``),
+        with the ``top_logprobs`` most likely alternatives per position.  HIP backend: the prefill forward with the
+        LM head, log-softmax and the target's logprob on the device per chunk (csrc/logprob.hip); the cache slots it
+        writes lose their prefix-cache records.  Torch backend: float64 log-softmax of the oracle's logits."""
+        n_top = int(top_logprobs or 0)
+        if not 0 <= n_top <= TOP_LOGPROBS_MAX:
+            raise ValueError(f"top_logprobs must be in 0..{TOP_LOGPROBS_MAX}, got {n_top}")
+        ids = [self.encode(p) or [self.cfg.bos_id] for p in prompts]
+        for p in ids:
+            if len(p) > self.T_max:
+                raise ValueError(f"prompt of {len(p)} tokens exceeds the context ({self.T_max})")
+        out: List[ScoreResult] = []
+        if self.backend == "torch":
+            for p in ids:
+                res = ScoreResult(list(p), [], [])
+                if len(p) > 1:
+                    lg = self.ref.forward(torch.tensor([p], device=self.device))[0].float().cpu()
+                    for j in range(1, len(p)):
+                        ls, top = logprob_host(lg[j - 1], n_top)
+                        res.logprobs.append(float(ls[p[j]]))
+                        res.top_logprobs.append(top)
+                out.append(res)
+            return out
+        for i in range(0, len(ids), self.max_batch):
+            group = ids[i:i + self.max_batch]
+            self._forget_slots(range(len(group)))
+            with torch.cuda.stream(self.stream):
+                lps, tops = self._prefill(group, score_top=n_top)
+            at = 0
+            for p in group:
+                n = len(p) - 1
+                out.append(ScoreResult(list(p), lps[at:at + n], tops[at:at + n]))
+                at += n
+        return out
+
     def _forget_slots(self, slots) -> None:
         """These slots are about to be written outside the continuous batch's bookkeeping: their records die."""
         for s in slots:
             self.slot_tokens[s] = []
 
-    def _prefill(self, ids, slots: Optional[Sequence[int]] = None, start: Optional[Sequence[int]] = None) -> None:
+    def _prefill(self, ids, slots: Optional[Sequence[int]] = None, start: Optional[Sequence[int]] = None,
+                 score_top: Optional[int] = None):
         """All prompt tokens but the last through the forward, into KV-cache slot ``slots[b]`` (default b).
         ``start[b]``: row b's slot already holds positions ``< start[b]`` of this prompt; tokens
-        ``ids[b][start[b]:-1]`` go in at positions ``start[b] ..`` (default: everything from 0)."""
-        flat_tok, flat_pos, flat_slot = [], [], []
+        ``ids[b][start[b]:-1]`` go in at positions ``start[b] ..`` (default: everything from 0).
+        ``score_top`` (``score``): every chunk also runs the LM head and scores each row's next token on the device,
+        with that many alternatives; returns the flat rows' (logprobs, top_logprobs)."""
+        flat_tok, flat_pos, flat_slot, flat_next = [], [], [], []
         for b, p in enumerate(ids):
             j0 = 0 if start is None else int(start[b])
             for j in range(j0, len(p) - 1):
                 flat_tok.append(p[j])
                 flat_pos.append(j)
                 flat_slot.append(b if slots is None else int(slots[b]))
+                flat_next.append(p[j + 1])
+        lps: List[float] = []
+        tops: List[List[tuple]] = []
         self.prefill_rows_total += len(flat_tok)
         pr = self.prefill_rows
         for c in range(0, len(flat_tok), self.prefill_chunk):
@@ -776,7 +963,21 @@ class DecodeEngine:
             pr["tok"][:n].copy_(torch.tensor(flat_tok[c:c + n], dtype=torch.int32))
             pr["pos"][:n].copy_(torch.tensor(flat_pos[c:c + n], dtype=torch.int32))
             pr["slot"][:n].copy_(torch.tensor(flat_slot[c:c + n], dtype=torch.int32))
-            self._forward(n, pr, want_logits=False, want_sample=False)
+            if score_top is None:
+                self._forward(n, pr, want_logits=False, want_sample=False)
+                continue
+            b = self._lp_bufs()
+            b["target"][:n].copy_(torch.tensor(flat_next[c:c + n], dtype=torch.int32))
+            b["s_topn"][:n].fill_(score_top)
+            self._forward(n, pr, want_logits=True, want_sample=False, lp=self._lp_struct(False, score_top))
+            lps += b["s_lp"][:n].cpu().tolist()
+            if score_top > 0:
+                ti, tl = b["s_top_id"][:n, :score_top].cpu().tolist(), b["s_top_lp"][:n, :score_top].cpu().tolist()
+                tops += [list(zip(a, v)) for a, v in zip(ti, tl)]
+            else:
+                tops += [[] for _ in range(n)]
+        if score_top is not None:
+            return lps, tops
 
     # ------------------------------------------------------------ continuous batching
     def continuous(self) -> "ContinuousBatch":
@@ -786,10 +987,13 @@ class DecodeEngine:
             raise RuntimeError("continuous batching needs the hip backend")
         return ContinuousBatch(self)
 
-    def _generate_torch(self, ids, nps, row_opts):
-        """Oracle backend with a KV cache (one token of compute per step), sampled on the host."""
+    def _generate_torch(self, ids, nps, row_opts, want=None):
+        """Oracle backend with a KV cache (one token of compute per step), sampled on the host; logprobs (``want``
+        per row: -1 or the number of alternatives) by ``logprob_host`` of the same logits."""
         t0 = time.perf_counter_ns()
         gens = []
+        with_lp = want is not None and any(w >= 0 for w in want)
+        lps: list = [([], []) if with_lp and want[i] >= 0 else None for i in range(len(ids))]
         for i, p in enumerate(ids):
             o = row_opts[i]
             rng = np.random.default_rng(o["seed"])
@@ -799,13 +1003,17 @@ class DecodeEngine:
             for _ in range(nps[i]):
                 logits = self.ref.forward(step, cache=cache, last_only=True)[0, -1].float().cpu()
                 nxt = sample_host(logits, out, o, rng)
+                if lps[i] is not None:
+                    ls, top = logprob_host(logits, want[i])
+                    lps[i][0].append(float(ls[nxt]))
+                    lps[i][1].append(top)
                 out.append(nxt)
                 step = torch.tensor([[nxt]], device=self.device)
                 if _stopped(out, o):
                     break
             gens.append(out)
         t1 = time.perf_counter_ns()
-        return gens, 0, t1 - t0
+        return gens, 0, t1 - t0, lps if with_lp else None
 
 
 SAMPLE_TOPK_MAX = 256  # the kernels' top-k clamp (csrc/sample.hip SS_KMAX): top_k <= 0 or above it means this many
@@ -876,6 +1084,7 @@ class ContinuousBatch:
         self.prompt_tokens: List[List[int]] = []
         self.options: List[Dict] = []
         self.reused: List[int] = []  # per live row: leading prompt tokens its slot already held at admit
+        self.want: List[int] = []  # per live row: -1 (no logprobs) or its number of top_logprobs
         # prefix-cache bookkeeping per live row (engine.slot_tokens): steps run since admit, the newest polled
         # token (its KV is not written yet), done at the last poll, last position already dropped from the record
         self._steps: List[int] = []
@@ -884,7 +1093,7 @@ class ContinuousBatch:
         self._trimmed: List[bool] = []
 
     def _row_lists(self):
-        return (self.row_slot, self.emitted, self.prompt_tokens, self.options, self.reused, self._steps,
+        return (self.row_slot, self.emitted, self.prompt_tokens, self.options, self.reused, self.want, self._steps,
                 self._pending, self._done, self._trimmed)
 
     def _trim_idled(self) -> None:
@@ -904,13 +1113,17 @@ class ContinuousBatch:
         return len(self.free_slots)
 
     def admit(self, prompts: Sequence[Union[str, Sequence[int]]], num_predict: Sequence[int],
-              options: Sequence[Optional[Dict]]) -> List[int]:
+              options: Sequence[Optional[Dict]], logprobs: Union[bool, Sequence[bool]] = False,
+              top_logprobs: Union[int, Sequence[int]] = 0) -> List[int]:
+        """``logprobs`` / ``top_logprobs`` per request (or one value for all) as ``DecodeEngine.generate``: rows that
+        ask and rows that do not decode together (``logprobs(row)`` reads a row's)."""
         from .. import ops
 
         eng = self.eng
         k = len(prompts)
         if k == 0:
             return []
+        want = _want_logprobs(logprobs, top_logprobs, k)
         if k > len(self.free_slots):
             raise ValueError(f"{k} requests but only {len(self.free_slots)} free rows")
         ids = [eng.encode(p) or [eng.cfg.bos_id] for p in prompts]
@@ -956,6 +1169,9 @@ class ContinuousBatch:
             r["done"][sl].zero_()
             r["max_new"][sl].copy_(torch.tensor(nps, dtype=torch.int32))
             eng.sample_params[ops.SAMPLE_BYTES * self.n: ops.SAMPLE_BYTES * (self.n + k)].copy_(ops.sample_params_tensor(row_opts, "cpu").to(eng.device))
+            if eng._lp is not None or any(w >= 0 for w in want):
+                eng._lp_bufs()["topn"][sl].copy_(torch.tensor(want, dtype=torch.int32))
+        self.want += want
         self.n += k
         self.row_slot += slots
         self.emitted += [0] * k
@@ -979,18 +1195,27 @@ class ContinuousBatch:
         stream_h = ctypes.c_void_p(eng.stream.cuda_stream)
         for i in range(self.n):
             self._steps[i] += steps
+        with_lp = any(w >= 0 for w in self.want)  # some live row wants logprobs: the graphs that compute them
         with torch.cuda.stream(eng.stream):
             k = eng.steps_per_graph
             if steps >= k:
-                g = eng._graph(self.n, k)
+                g = eng._graph(self.n, k, with_lp)
                 for _ in range(steps // k):
                     if eng.lib.cain_graph_launch(ctypes.c_void_p(g), stream_h) != 0:
                         raise RuntimeError("hipGraphLaunch failed")
             if steps % k:
-                g1 = eng._graph(self.n, 1)
+                g1 = eng._graph(self.n, 1, with_lp)
                 for _ in range(steps % k):
                     if eng.lib.cain_graph_launch(ctypes.c_void_p(g1), stream_h) != 0:
                         raise RuntimeError("hipGraphLaunch failed")
+
+    def logprobs(self, row: int, lo: int = 0, hi: Optional[int] = None):
+        """``(logprobs, top_logprobs)`` of tokens ``lo .. hi - 1`` (default: all polled so far) of a live row that
+        asked for them; None for a row that did not."""
+        if self.want[row] < 0:
+            return None
+        with torch.cuda.stream(self.eng.stream):
+            return self.eng._read_logprobs(row, lo, self.emitted[row] if hi is None else hi, self.want[row])
 
     def poll(self):
         """([new token ids per live row], [finished flag per live row])."""
@@ -1057,6 +1282,9 @@ class ContinuousBatch:
 
                 sp = eng.sample_params.view(-1, ops.SAMPLE_BYTES)
                 sp[dst] = sp[src]
+                if eng._lp is not None:
+                    for key in ("topn", "lp", "top_id", "top_lp"):
+                        eng._lp[key][dst] = eng._lp[key][src]
             for j, h in moves.items():
                 for lst in self._row_lists():
                     lst[h] = lst[j]

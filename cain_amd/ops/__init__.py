@@ -24,6 +24,7 @@ op                     source                      replaces (Ollama/llama.cpp)
 ``attention``          csrc/attention.hip          decode / prefill attention (split-K, in-kernel combine)
 ``kv_copy_prefix``     csrc/kv_prefix.hip          a slot's cached prompt prefix copied to another slot
 ``sample``             csrc/sample.hip             repeat-penalty/temperature/top-k/top-p
+``logprob_rows``       csrc/logprob.hip            log-softmax, top-n and token logprobs on device
 ``Plan``               csrc/runtime.hip            per-step schedule + hipGraph replay
 =====================  ==========================  =============================
 """
@@ -160,6 +161,14 @@ def load() -> ctypes.CDLL:
         lib.cain_stream_create_cu_limited.argtypes = [ci]
         lib.cain_stream_destroy.argtypes = [vp]
         lib.cain_kv_copy_prefix.argtypes = [vp, vp, ctypes.c_longlong, ci, ci, ci, ci, ci, ci, vp, vp, vp, ci, vp]
+        lib.cain_logprob_rows.argtypes = [vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        lib.cain_logprob_pre.argtypes = [vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp]
+        lib.cain_logprob_chosen.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, vp]
+        lib.cain_logprob_keep_bytes.restype = ctypes.c_longlong
+        lib.cain_logprob_keep_bytes.argtypes = [ci]
+        lib.cain_plan_forward_lp.argtypes = [vp, ci, vp, ci, ci, vp, vp]
+        lib.cain_plan_capture_lp.restype = vp
+        lib.cain_plan_capture_lp.argtypes = [vp, ci, vp, ci, vp, vp, ctypes.POINTER(ci)]
         if os.environ.get("CAIN_WGEMM_INLINE") and hasattr(real, "cain_wgemm_set_inline"):  # A/B runs
             real.cain_wgemm_set_inline(int(os.environ["CAIN_WGEMM_INLINE"]))
         if os.environ.get("CAIN_SAMPLE_CM"):  # A/B runs (set_sample_cm)
@@ -897,6 +906,63 @@ def sample(logits, tok, pos, gen, n_gen, max_new, done, hist, slot, params, T_ma
         return
     _check(lib.cain_sample(_p(logits), logits.stride(0), V, _p(tok), _p(pos), _p(gen), gen.stride(0), _p(n_gen),
                            _p(max_new), _p(done), _p(hist), _p(slot), T_max, M, _p(params), _stream()), "sample")
+
+
+LOGPROB_TOP_MAX = 20  # top_logprobs limit: entries per token in the top-n buffers (csrc/logprob.hip LP_TOP)
+
+
+def _lp_nmax(topn: torch.Tensor, nmax: Optional[int]) -> int:
+    return int(nmax) if nmax is not None else max(0, int(topn.max()))
+
+
+def logprob_rows(logits: torch.Tensor, V: int, topn: torch.Tensor, slot=None, done=None, target=None, lse=None,
+                 lp=None, top_id=None, top_lp=None, nmax: Optional[int] = None) -> int:
+    """Log-softmax statistics of fp32 logits rows ``[M, ldl]`` (``ldl = logits.stride(0) >= V``; csrc/logprob.hip):
+    per row m with ``topn[m] >= 0`` (and ``slot[m] >= 0``, ``done[m] == 0`` where given) the log-sum-exp into
+    ``lse[m]``, the natural-log softmax of ``target[m]`` into ``lp[m]`` and the ``topn[m]`` most likely ids (logit
+    descending, index ascending on ties) with their logprobs into ``top_id / top_lp[m, :topn[m]]`` (``[M, 20]``).
+    Other rows are left as they are.  ``nmax``: the largest ``topn`` (default: read from the device).  Returns the
+    entry's code: 0, or non-zero when it refused the arguments (``V % 4``, ``ldl < V``, ``nmax > 20``) with nothing
+    launched."""
+    lib = load()
+    _gpu(logits, topn)
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and topn.dtype == torch.int32
+    for t in (top_id, top_lp):
+        assert t is None or (t.is_contiguous() and t.shape[-1] == LOGPROB_TOP_MAX)
+    return int(lib.cain_logprob_rows(_p(logits), logits.stride(0), int(V), logits.shape[0], _p(slot), _p(done),
+                                     _p(topn), _lp_nmax(topn, nmax), _p(target), _p(lse), _p(lp), _p(top_id),
+                                     _p(top_lp), _stream()))
+
+
+def logprob_keep(M: int, device) -> torch.Tensor:
+    """Scratch that ``logprob_pre`` hands to ``logprob_chosen`` for M rows."""
+    return torch.zeros(int(load().cain_logprob_keep_bytes(int(M))), device=device, dtype=torch.uint8)
+
+
+def logprob_pre(logits: torch.Tensor, V: int, topn: torch.Tensor, n_gen, hist, gen: torch.Tensor, top_id, top_lp,
+                keep, slot=None, done=None, nmax: Optional[int] = None) -> int:
+    """The decode step's statistics, BEFORE the sampler (which may apply the repeat penalty in place on ``logits``):
+    the top-n of each wanted live row into the rings at the index of the token about to be generated,
+    ``top_id / top_lp[m, n_gen[m], :topn[m]]`` (``[M, ldg, 20]``, ``ldg = gen.stride(0)``), and into ``keep``
+    (``logprob_keep``) the row's log-sum-exp, ``n_gen`` and the raw logits of its history ids."""
+    lib = load()
+    _gpu(logits, topn, keep)
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and topn.dtype == torch.int32
+    assert top_id.is_contiguous() and top_lp.is_contiguous() and top_id.shape[-1] == LOGPROB_TOP_MAX
+    assert keep.numel() >= int(lib.cain_logprob_keep_bytes(logits.shape[0]))
+    return int(lib.cain_logprob_pre(_p(logits), logits.stride(0), int(V), logits.shape[0], _p(slot), _p(done),
+                                    _p(topn), _lp_nmax(topn, nmax), _p(n_gen), _p(hist), gen.stride(0), _p(top_id),
+                                    _p(top_lp), _p(keep), _stream()))
+
+
+def logprob_chosen(logits: torch.Tensor, V: int, gen: torch.Tensor, keep, lp: torch.Tensor) -> int:
+    """AFTER the sampler: ``lp[m, n]`` = the logprob of the token the sampler wrote at ``gen[m, n]`` (n: the row's
+    ``n_gen`` before the step), from the raw logit ``logprob_pre`` kept when the id is one of the history ids."""
+    lib = load()
+    _gpu(logits, gen, keep, lp)
+    assert lp.stride(0) == gen.stride(0) and lp.dtype == torch.float32
+    return int(lib.cain_logprob_chosen(_p(logits), logits.stride(0), int(V), logits.shape[0], _p(gen), gen.stride(0),
+                                       _p(keep), _p(lp), _stream()))
 
 
 _SAMPLE_WS: dict = {}

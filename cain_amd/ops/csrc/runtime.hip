@@ -80,6 +80,14 @@ CAIN_API int cain_gemm_cmax_take();
 CAIN_API int cain_sample_ex(float* logits, int ldl, int V, int* tok, int* pos, int* gen, int ldg, int* n_gen,
                             const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
                             const void* params, void* ws, long long ws_bytes, hipStream_t st);
+CAIN_API int cain_logprob_rows(const float* logits, int ldl, int V, int M, const int* slot, const int* done,
+                               const int* topn, int nmax, const int* target, float* lse, float* lp, int* top_id,
+                               float* top_lp, hipStream_t st);
+CAIN_API int cain_logprob_pre(const float* logits, int ldl, int V, int M, const int* slot, const int* done,
+                              const int* topn, int nmax, const int* n_gen, const int* hist, int ldg, int* top_id,
+                              float* top_lp, void* keep, hipStream_t st);
+CAIN_API int cain_logprob_chosen(const float* logits, int ldl, int V, int M, const int* gen, int ldg, const void* keep,
+                                 float* lp, hipStream_t st);
 
 extern "C" {
 
@@ -169,6 +177,21 @@ struct CainRows {
   const void* sample_params;
 };
 
+// Token log-probabilities of a forward (logprob.hip; cain_plan_forward_lp / cain_plan_capture_lp).  Decode forwards
+// (want_sample): the statistics and the top-n run between the LM head and the sampler, the sampled token's logprob
+// after it, into rings indexed like CainRows::gen: lp[m * ldg + n], top_id / top_lp[(m * ldg + n) * 20 + j].
+// Forwards with logits but no sampler (teacher forcing): `target` names each row's token, results are per row:
+// lp[m], top_id / top_lp[m * 20 + j].
+struct CainLogprob {
+  const int* topn;  // per row: -1 not wanted, else how many alternatives (0 .. 20)
+  int nmax;         // the largest of them
+  float* lp;
+  int* top_id;
+  float* top_lp;
+  void* keep;         // decode: cain_logprob_keep_bytes(M) of scratch between the two launches
+  const int* target;  // teacher forcing
+};
+
 }  // extern "C"
 
 namespace {
@@ -213,7 +236,9 @@ int max_rows(const CainPlanDesc& d) {
 
 // 5 launches per layer: QKV(+RMSNorm, bias, RoPE, KV append) -> attention(+combine) ->
 // O(+residual) -> gate/up(+RMSNorm, act*mul) -> down(+residual); 6 in a layer whose V rows are Q6_K beside Q4 q / k.
-int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_sample, hipStream_t st) {
+// lq: the caller's logprob buffers (null: none -- the launches are exactly those of a plan without the feature)
+int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_sample, hipStream_t st,
+            const CainLogprob* lq = nullptr) {
   const CainPlanDesc& d = p.d;
   const int qkv_dim = (d.H + 2 * d.Hkv) * d.hd;
   const int q_dim = d.H * d.hd;
@@ -304,6 +329,13 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
             /*EPI_F32*/ 2, d.flm_head));
   }
   const bool cm = want_logits && cain_gemm_cmax_take();
+  if (lq && !want_logits) return -1;
+  if (lq && want_sample)  // before the sampler: two of its kernels apply the repeat penalty in place on the logits
+    CK(cain_logprob_pre(d.logits, d.V, d.V, M, r.slot, r.done, lq->topn, lq->nmax, r.n_gen, r.hist, r.ldg, lq->top_id,
+                        lq->top_lp, lq->keep, st));
+  if (lq && !want_sample)
+    CK(cain_logprob_rows(d.logits, d.V, d.V, M, r.slot, nullptr, lq->topn, lq->nmax, lq->target, nullptr, lq->lp,
+                         lq->top_id, lq->top_lp, st));
   if (want_sample) {
     // the chunk-max sampler refuses (< 0) vocabularies beyond its chunk capacity: the two-stage / one-workgroup
     // kernels take those
@@ -317,6 +349,7 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
     if (e < 0)
       CK(cain_sample_ex(d.logits, d.V, d.V, r.tok, r.pos, r.gen, r.ldg, r.n_gen, r.max_new, r.done, r.hist, r.slot,
                         d.T_max, M, r.sample_params, p.sample_ws, p.sample_ws_bytes, st));
+    if (lq) CK(cain_logprob_chosen(d.logits, d.V, d.V, M, r.gen, r.ldg, lq->keep, lq->lp, st));
   }
   return 0;
 }
@@ -361,8 +394,19 @@ CAIN_API int cain_plan_forward(void* plan, int M, const CainRows* rows, int want
   return forward(*p, M, *rows, want_logits, want_sample, st);
 }
 
-// Record `steps` decode steps over M rows into a graph; returns the executable graph (or null).
-CAIN_API void* cain_plan_capture(void* plan, int M, const CainRows* rows, int steps, hipStream_t st, int* err) {
+// The same forward with token log-probabilities (CainLogprob): needs want_logits; a null `lq` is cain_plan_forward.
+CAIN_API int cain_plan_forward_lp(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
+                                  const CainLogprob* lq, hipStream_t st) {
+  auto* p = static_cast<Plan*>(plan);
+  g_fail[0] = 0;
+  if (M < 1 || M > max_rows(p->d)) return -1;
+  return forward(*p, M, *rows, want_logits, want_sample, st, lq);
+}
+
+// Record `steps` decode steps over M rows into a graph; returns the executable graph (or null).  Each step with its
+// token log-probabilities when `lq` is given (null: the graph of cain_plan_capture, launch for launch).
+CAIN_API void* cain_plan_capture_lp(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
+                                    hipStream_t st, int* err) {
   auto* p = static_cast<Plan*>(plan);
   *err = 0;
   if (M < 1 || M > max_rows(p->d) || steps < 1) {
@@ -376,7 +420,7 @@ CAIN_API void* cain_plan_capture(void* plan, int M, const CainRows* rows, int st
     return nullptr;
   }
   int fe = 0;
-  for (int s = 0; s < steps && fe == 0; ++s) fe = forward(*p, M, *rows, 1, 1, st);
+  for (int s = 0; s < steps && fe == 0; ++s) fe = forward(*p, M, *rows, 1, 1, st, lq);
   e = hipStreamEndCapture(st, &g);
   if (fe != 0 || e != hipSuccess) {
     *err = fe ? fe : int(e);
@@ -391,6 +435,10 @@ CAIN_API void* cain_plan_capture(void* plan, int M, const CainRows* rows, int st
     return nullptr;
   }
   return ex;
+}
+
+CAIN_API void* cain_plan_capture(void* plan, int M, const CainRows* rows, int steps, hipStream_t st, int* err) {
+  return cain_plan_capture_lp(plan, M, rows, steps, nullptr, st, err);
 }
 
 CAIN_API int cain_graph_launch(void* exec, hipStream_t st) {
@@ -449,6 +497,7 @@ CAIN_API void* cain_stream_create_cu_limited(int n_cu) {
 CAIN_API int cain_stream_destroy(void* st) { return hipStreamDestroy(static_cast<hipStream_t>(st)) == hipSuccess ? 0 : -1; }
 
 CAIN_API int cain_rows_size() { return int(sizeof(CainRows)); }
+CAIN_API int cain_logprob_size() { return int(sizeof(CainLogprob)); }
 CAIN_API int cain_plan_desc_size() { return int(sizeof(CainPlanDesc)); }
 CAIN_API int cain_layer_size() { return int(sizeof(CainLayer)); }
 

@@ -8,7 +8,8 @@ validates, and runs the experiment; any other first argument is a command.
 Commands: ``help``, ``config-create [dir]``, ``prepare`` (build the native
 libraries and HIP kernels in-tree), ``analyze <run_table.csv>`` (paper tables),
 ``serve`` (Ollama-compatible server on this host's GPU), ``generate``
-(one local generation, prints Ollama-style JSON).
+(one local generation, prints Ollama-style JSON), ``perplexity`` (a text's perplexity
+under a model, one JSON line).
 
 Run options (new): ``--gpus N`` fans TODO rows out data-parallel over N GPU
 worker processes (``cain_amd.parallel``; ``--max-restarts`` relaunches after a
@@ -107,6 +108,13 @@ def cmd_generate(args: List[str]) -> None:
     server.generate_main(args)
 
 
+def cmd_perplexity(args: List[str]) -> None:
+    """Perplexity of a text under a model, on any weight / KV format: one JSON line (engine/perplexity.py)."""
+    from ..engine import perplexity
+
+    perplexity.main(args)
+
+
 def cmd_convert(args: List[str]) -> None:
     """``convert <checkpoint dir | .gguf> <out.gguf> [--type F16]``: a checkpoint as a GGUF file with llama.cpp's
     conventions (models/gguf.py export_gguf), e.g. to run the same weights under llama.cpp / Ollama.  A Hugging Face
@@ -160,6 +168,8 @@ COMMANDS = {
     "analyze": ("<run_table.csv> [--out DIR]", cmd_analyze),
     "serve": ("[--host H] [--port P] [--models m1,m2] [--device N] [--prefix-cache]", cmd_serve),
     "generate": ("--model M --prompt P [--num-predict N] [--checkpoint PATH]", cmd_generate),
+    "perplexity": ("--model TAG [--checkpoint PATH] [--weights W] [--kv K] (--file PATH | --prompt TEXT) [--ctx N] "
+                   "[--batch B]", cmd_perplexity),
     "convert": ("<checkpoint dir | .gguf> <out.gguf> [--type F16|Q8_0|Q4_0|Q4_K|Q6_K|Q4_K_M|...]", cmd_convert),
     "help": ("", cmd_help),
 }

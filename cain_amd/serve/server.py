@@ -32,6 +32,13 @@ the best matching slot (engine.plan_prefix_reuse): a chat's next turn, or reques
 the shared prefix; the final JSON then carries ``prompt_cached_count``.  Off by default: responses keep their size
 and every request computes its whole prompt, as the study's measurements assume.
 
+Log-probabilities: ``"logprobs": true`` (and ``"top_logprobs": n``, 0 .. 20) on ``/api/generate`` and ``/api/chat``
+adds ``"logprobs": [{"token", "logprob", "bytes", "id", "top_logprobs": [{"token", "logprob", "bytes", "id"}]}]`` to
+the response, one entry per generated token (streaming: each piece carries the entries of its own tokens).  A token's
+logprob is the natural-log softmax of the model's own logits: temperature 1, before the repeat penalty and top-k /
+top-p; the alternatives are the n most likely tokens of that distribution.  ``id`` (the token id) is this server's
+addition: random-weight vocabularies detokenise badly.  Requests that do not ask get exactly the keys they always got.
+
 Tracing: started with ``--trace-dir DIR``, the engine backend records every decode batch
 with ``torch.profiler`` (host ops + GPU kernels) and writes a Chrome trace to DIR; the response JSON
 names it in ``cain_trace`` so the client can file it with its run (the study moves it into run_dir).
@@ -86,6 +93,18 @@ class Job:
     trace_file: Optional[str] = None  # Chrome trace of the batch that decoded this job (--trace-dir)
     context: Optional[List[int]] = None  # token ids that go in front of the prompt's (Ollama's ``context``)
     want_context: bool = False       # the response carries ``context``
+    logprobs: bool = False           # the response carries ``logprobs`` (one entry per generated token)
+    top_logprobs: int = 0            # alternatives per entry (0 .. 20)
+    lp_entries: List[Dict[str, Any]] = field(default_factory=list)  # the entries produced so far
+
+
+def logprob_entries(tok, ids, lps, tops) -> List[Dict[str, Any]]:
+    """The response's ``logprobs`` entries of tokens ``ids`` with logprobs ``lps`` and alternatives ``tops``."""
+    def one(i: int, lp: float) -> Dict[str, Any]:
+        text = tok.decode([int(i)])
+        return {"token": text, "logprob": float(lp), "bytes": list(text.encode("utf-8")), "id": int(i)}
+
+    return [dict(one(i, lp), top_logprobs=[one(a, v) for a, v in top]) for i, lp, top in zip(ids, lps, tops)]
 
 
 class Backend:
@@ -117,6 +136,7 @@ class Backend:
         return None
 
     prefix_cache = False
+    logprobs = True  # requests may ask for token log-probabilities
 
 
 # Ollama's quantization_level names for the engine's weight storage
@@ -244,17 +264,23 @@ class EngineBackend(Backend):
         streams = [j.stream for j in jobs]
         decs = [StreamDecoder(tok) for _ in jobs]
 
-        def on_tokens(new_per_row: List[List[int]]) -> None:
-            for j, d, ids in zip(jobs, decs, new_per_row):
+        def on_tokens(new_per_row: List[List[int]], lps=None) -> None:
+            for r, (j, d, ids) in enumerate(zip(jobs, decs, new_per_row)):
                 if j.stream is not None and ids:
                     piece = d.push(ids)
-                    if piece:
+                    if j.logprobs:  # the entries of this piece's tokens travel with it (the text may be held back)
+                        ents = logprob_entries(tok, ids, *lps[r])
+                        j.lp_entries += ents
+                        j.stream((piece, ents))
+                    elif piece:
                         j.stream(piece)
 
         def gen():
+            kw = dict(logprobs=[j.logprobs for j in jobs], top_logprobs=[j.top_logprobs for j in jobs]) \
+                if any(j.logprobs for j in jobs) else {}
             return eng.generate([j.prompt for j in jobs], [j.num_predict for j in jobs], [j.options for j in jobs],
                                 on_tokens=on_tokens if any(streams) else None,
-                                context=[j.context for j in jobs] if any(j.context for j in jobs) else None)
+                                context=[j.context for j in jobs] if any(j.context for j in jobs) else None, **kw)
 
         if self.trace_dir:
             res, path = self._traced(model, gen)
@@ -268,6 +294,8 @@ class EngineBackend(Backend):
                 tail = d.flush()  # text held back at a length cutoff inside a character
                 if tail:
                     j.stream(tail)
+            if j.logprobs and j.stream is None:
+                j.lp_entries = logprob_entries(tok, r.tokens, r.logprobs, r.top_logprobs)
             j.result = r
             j.ttft_ns = ttft
 
@@ -328,7 +356,8 @@ class EngineBackend(Backend):
             ids.append(p)
         if ok:
             t0 = time.perf_counter_ns()
-            rows = cb.admit(ids, [j.num_predict for j in ok], [j.options for j in ok])
+            rows = cb.admit(ids, [j.num_predict for j in ok], [j.options for j in ok],
+                            [j.logprobs for j in ok], [j.top_logprobs for j in ok])
             eng.stream.synchronize()
             t_pre = time.perf_counter_ns()
             cb.step(1)  # the new rows' first token on its own (the live rows advance one step with them)
@@ -340,10 +369,15 @@ class EngineBackend(Backend):
         new, fin = cb.poll()
         now = time.perf_counter_ns()
         for r, new_ids in enumerate(new):
-            if new_ids and live[r]["job"].stream is not None:
+            j = live[r]["job"]
+            if new_ids and j.logprobs:
+                j.lp_entries += logprob_entries(tok, new_ids, *cb.logprobs(r, cb.emitted[r] - len(new_ids)))
+            if new_ids and j.stream is not None:
                 piece = live[r]["dec"].push(new_ids)
-                if piece:
-                    live[r]["job"].stream(piece)
+                if j.logprobs:
+                    j.stream((piece, j.lp_entries[-len(new_ids):]))
+                elif piece:
+                    j.stream(piece)
         done_rows = [r for r, f in enumerate(fin) if f]
         for r in done_rows:
             st, j = live[r], live[r]["job"]
@@ -389,6 +423,8 @@ class EngineBackend(Backend):
 class FakeBackend(Backend):
     """Canned generations with controllable latency (tests / plumbing runs without a GPU).
     ``fail`` makes every request raise; ``hang_s`` sleeps before answering (timeout tests)."""
+
+    logprobs = False  # no model behind this backend: nothing to take a probability from
 
     def __init__(self, models=("qwen2:1.5b",), tokens_per_s: float = 2000.0, prefill_s: float = 0.0,
                  fail: bool = False, hang_s: float = 0.0):
@@ -494,6 +530,8 @@ def _result_json(job: Job, created: Optional[str] = None) -> Dict[str, Any]:
     d["cain_ttft_ns"] = int(getattr(job, "ttft_ns", 0))
     if job.trace_file:
         d["cain_trace"] = job.trace_file
+    if job.logprobs:
+        d["logprobs"] = list(job.lp_entries)
     return d
 
 
@@ -588,6 +626,15 @@ class OllamaHandler(BaseHTTPRequestHandler):
                 return self._send_json(400, {"error": "context must be a list of token ids"})
             if any(t < 0 or (vocab is not None and t >= vocab) for t in context):
                 return self._send_json(400, {"error": f"context holds a token id outside the vocabulary ({vocab})"})
+        want_lp, n_top = body.get("logprobs", False), body.get("top_logprobs", 0)
+        if not isinstance(want_lp, bool):
+            return self._send_json(400, {"error": "logprobs must be true or false"})
+        if isinstance(n_top, bool) or not isinstance(n_top, int) or not 0 <= n_top <= 20:
+            return self._send_json(400, {"error": "top_logprobs must be an integer in 0..20"})
+        if n_top and not want_lp:
+            return self._send_json(400, {"error": "top_logprobs needs logprobs: true"})
+        if want_lp and not getattr(self.scheduler.backend, "logprobs", False):
+            return self._send_json(400, {"error": "logprobs: no model behind this backend"})
         opts = dict(body.get("options") or {})
         n = opts.get("num_predict")
         # the length policy reads the user's words ("In N words ..."), not the template around them
@@ -597,7 +644,8 @@ class OllamaHandler(BaseHTTPRequestHandler):
         chunks: "queue.Queue[str]" = queue.Queue()
         job = Job(model, prompt, num_predict, opts, stream=chunks.put if stream else None, context=context,
                   want_context=not chat and (context is not None or bool(getattr(self.scheduler.backend,
-                                                                                "prefix_cache", False))))
+                                                                                "prefix_cache", False))),
+                  logprobs=want_lp, top_logprobs=n_top)
         try:
             self.scheduler.submit(job)
         except KeyError as exc:
@@ -626,7 +674,12 @@ class OllamaHandler(BaseHTTPRequestHandler):
                 piece = chunks.get(timeout=0.05)
             except queue.Empty:
                 continue
+            ents = None
+            if isinstance(piece, tuple):
+                piece, ents = piece
             part = {"model": model, "created_at": _now(), "done": False}
+            if ents is not None:
+                part["logprobs"] = ents
             if chat:
                 part["message"] = {"role": "assistant", "content": piece}
             else:
@@ -637,6 +690,8 @@ class OllamaHandler(BaseHTTPRequestHandler):
         else:
             d = _result_json(job, created)
             d["response"] = ""
+            if job.logprobs:
+                d["logprobs"] = []  # every entry went out with its piece
             if chat:
                 d.pop("response")
                 d["message"] = {"role": "assistant", "content": ""}
