@@ -366,11 +366,11 @@ class DecodeEngine:
         above (wgemm8.hip FP4: the same bytes on the block-scaled fp4 x fp8 MFMA, activations per row to e4m3) up to
         256; every GEMM K (d_model, q_dim, ffn) must be a multiple of 128 (>= 512 for W4A8).
         ``weight_dtype="q4_0" / "q4_k"``: llama.cpp's GGUF 4-bit blocks (Ollama's default builds) run natively
-        (gemm_q4.hip: the block values as stored, scales applied per block; forwards of more rows than its LDS copy
+        (gemm_qstream.hip: the block values as stored, scales applied per block; forwards of more rows than its LDS copy
         holds on gemm_qtile.hip, one pass over the weights per 64 rows) up to 64 rows per
         forward; every GEMM K must be a multiple of 256.
         ``weight_dtype="q4_k_m"``: Q4_K with the output head and the attn_v / ffn_down matrices of part of the
-        layers in Q6_K (gemm_q6.hip), the mix of Ollama's default Q4_K_M files (models/gguf.py q4_k_m_type) -- what
+        layers in Q6_K (gemm_qstream.hip), the mix of Ollama's default Q4_K_M files (models/gguf.py q4_k_m_type) -- what
         random-init and Hugging Face weights are laid out in.  A GGUF file loaded on ``q4_k`` or ``q4_k_m`` keeps
         whatever mix of Q4_K and Q6_K tensors it stores (``weights.native["requantized"]`` lists the tensors of any
         other type -- Q5_K, Q8_0, F16 ... -- and a Q6_K gate / up, which are re-quantised to Q4_K); a layer whose V

@@ -1,4 +1,4 @@
-"""GGUF 4-bit weights (llama.cpp's Q4_0 and Q4_K) for the native Q4 kernel (``ops/csrc/gemm_q4.hip``).
+"""GGUF 4-bit weights (llama.cpp's Q4_0 and Q4_K) for the native Q4 kernel (``ops/csrc/gemm_qstream.hip``).
 
 The reference's models are Ollama pulls whose default builds are Q4_0 / Q4_K_M GGUF files
 (/root/reference/README.md:29-30; tags at /root/reference/experiment/RunnerConfig.py:80).  Round 5 dequantised such
@@ -8,7 +8,7 @@ them and only their layout changes:
 * ``q4_fields``: ggml block bytes -> codes (uint8 0..15 per weight) plus the block scales -- Q4_0: fp16 ``d`` per 32;
   Q4_K: 6-bit ``sc`` / ``m`` per 32 and fp16 ``d`` / ``dmin`` per 256 (decoded as ggml's ``get_scale_min_k4``,
   ``gguf._k_scale_min``);
-* ``pack_q4``: the fields -> the kernel's tile layout (gemm_q4.hip header), one byte buffer of scales
+* ``pack_q4``: the fields -> the kernel's tile layout (gemm_qstream.hip header), one byte buffer of scales
   ``[sc: N K / 16][Q4_K (d, dmin): N K / 64][optional fp32 gain: K]``;
 * ``quantize_q4_0`` / ``quantize_q4_k``: weights -> ggml block bytes (random-init models in a GGUF format: the
   bench's ``--weights q4_0 / q4_k`` rows), ``dequantize_q4``: bytes -> fp32 (gguf.py's decoders, the oracle).
@@ -17,7 +17,7 @@ Q4_K's quantiser is a plain min/max fit (per 32: scale (max - min) / 15, min -mi
 / 63), not llama.cpp's iterative ``make_qkx2_quants`` search: the kernel runs whatever valid blocks a file holds,
 and random weights only need valid blocks of the right layout.
 
-Q6_K (format id ``Q6_K`` = 2; ``ops/csrc/gemm_q6.hip``) is the type a Q4_K_M file keeps its output head and part of
+Q6_K (format id ``Q6_K`` = 2; ``ops/csrc/gemm_qstream.hip``) is the type a Q4_K_M file keeps its output head and part of
 its ``attn_v`` / ``ffn_down`` tensors in: ``q6_fields`` / ``pack_q6`` / ``quantize_q6_k`` are its members of the same
 three steps, ``gguf_q4_native`` keeps such tensors as stored beside the plan's 4-bit format, and ``q4_k_m_formats``
 is the per-matrix mix ``weight_dtype="q4_k_m"`` lays random or Hugging Face weights out in.
@@ -30,8 +30,8 @@ import torch
 
 from .gguf import _k_scale_min, dequantize
 
-Q4_FORMATS = {"q4_0": 0, "q4_k": 1}  # gemm_q4.hip Q4F_*
-Q6_K = 2                              # gemm_q6.hip Q6F_K
+Q4_FORMATS = {"q4_0": 0, "q4_k": 1}  # csrc/gemm_q.h Q4F_*
+Q6_K = 2                              # csrc/gemm_q.h Q6F_K
 _BLOCK_BYTES = {0: 18, 1: 144, 2: 210}
 _BLOCK_ELEMS = {0: 32, 1: 256, 2: 256}
 GGML_TYPE = {0: 2, 1: 12, 2: 14}  # ggml type ids of Q4_0 / Q4_K / Q6_K
@@ -151,7 +151,7 @@ def q6_fields(blocks: torch.Tensor, n: int, k: int) -> Dict[str, torch.Tensor]:
 
 
 def pack_q6(fields: Dict[str, torch.Tensor], gain: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``q6_fields`` -> (codes uint8 [N / 16, K / 128, 1536], scale buffer uint8) in gemm_q6.hip's layout: per (tile,
+    """``q6_fields`` -> (codes uint8 [N / 16, K / 128, 1536], scale buffer uint8) in gemm_qstream.hip's layout: per (tile,
     128-k quad) [64 lanes x 16 bytes of low nibbles][64 lanes x 8 bytes of high bit pairs], lane l = 16 g + r holding
     row 16 t + r; group s of the quad (k = 128 p + 16 s + 4 g + j) sits in byte j of low dword s >> 1 (nibble s & 1)
     and of high dword s >> 2 (bits 2 (s & 3)).  The scale buffer is [per (t, p, r): 8 int8 group scales][per (t,
@@ -178,7 +178,7 @@ def pack_q6(fields: Dict[str, torch.Tensor], gain: Optional[torch.Tensor] = None
 
 def pack_q4(fields: Dict[str, torch.Tensor], fmt: int, gain: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor,
                                                                                                       torch.Tensor]:
-    """``q4_fields`` -> (codes uint8 [N / 16, K / 128, 64, 16], scale buffer uint8) in gemm_q4.hip's layout: lane
+    """``q4_fields`` -> (codes uint8 [N / 16, K / 128, 64, 16], scale buffer uint8) in gemm_qstream.hip's layout: lane
     l = 16 g + r of quad p holds row 16 t + r, k = 128 p + 32 s + 8 g + j at dword s, byte j & 3, nibble j >> 2; the
     scale buffer is [per (t, p, r): 4 x 2 bytes of block scales][Q4_K: per (t, super-block, r) (d, dmin)][gain]."""
     codes = fields["codes"]
@@ -240,7 +240,7 @@ def gguf_q4_native(g, cfg, fmt: int, device="cpu") -> Dict[str, object]:
     each matrix's format id is recorded under ``fmts``.  The fused QKV takes one format: where V's differs from q /
     k's (Q4_K_M), V is returned on its own under ``wv`` and ``wqkv`` holds the q and k rows only.  What is
     quantised to ``fmt`` from its decoded values instead, and listed under ``requantized``: tensors of any other
-    type (Q5_K, Q8_0, F16 ...), q and k when their types differ from each other, and a Q6_K gate / up (gemm_q6.hip
+    type (Q5_K, Q8_0, F16 ...), q and k when their types differ from each other, and a Q6_K gate / up (gemm_qstream.hip
     has no gate/up activation epilogue).  Result: {"fmt", "layers": [{wqkv, [wv,] wo, w_gate, w_up, w_down, fmts}],
     "lm_head", "lm_head_fmt", "requantized"}, attached to ``ModelWeights.native`` for ``pack_for_engine``."""
     import numpy as np

@@ -364,8 +364,8 @@ def roundtrip_weights(mw: ModelWeights, weight_dtype: str) -> ModelWeights:
     return mw
 
 
-# q4_0 / q4_k: llama.cpp's GGUF block formats (models/q4.py, ops/csrc/gemm_q4.hip), Ollama's default builds;
-# q4_k_m: Q4_K with the output head and part of the V / down projections in Q6_K (ops/csrc/gemm_q6.hip), the mix
+# q4_0 / q4_k: llama.cpp's GGUF block formats (models/q4.py, ops/csrc/gemm_qstream.hip), Ollama's default builds;
+# q4_k_m: Q4_K with the output head and part of the V / down projections in Q6_K (ops/csrc/gemm_qstream.hip), the mix
 # Ollama's default Q4_K_M files store
 WEIGHT_DTYPES = ("bf16", "fp8", "fp4", "q4_0", "q4_k", "q4_k_m")
 

@@ -17,8 +17,8 @@ op                     source                      replaces (Ollama/llama.cpp)
 ``gemm_w8``            csrc/gemm_w8.hip            the same GEMMs on fp8 (e4m3) weights, <= 64 rows
 ``gemm_w8a8``          csrc/wgemm8.hip             fp8 weights x per-row fp8 activations, 16 < M <= 256
 ``gemm_w4``            csrc/gemm_w4.hip            the same GEMMs on MXFP4 (e2m1 + e8m0) weights, <= 64 rows
-``gemm_q4``            csrc/gemm_q4.hip            the same GEMMs on GGUF Q4_0 / Q4_K blocks (exact values), any M
-``gemm_q6``            csrc/gemm_q6.hip            the same on GGUF Q6_K blocks (a Q4_K_M file's 6-bit tensors), any M
+``gemm_q4``            csrc/gemm_qstream.hip       the same GEMMs on GGUF Q4_0 / Q4_K blocks (exact values), any M
+``gemm_q6``            csrc/gemm_qstream.hip       the same on GGUF Q6_K blocks (a Q4_K_M file's 6-bit tensors), any M
 ``rmsnorm``            csrc/norm.hip               RMSNorm (standalone; the engine fuses it)
 ``embed``              csrc/norm.hip               embedding gather (+Gemma scale)
 ``attention``          csrc/attention.hip          decode / prefill attention (split-K, in-kernel combine)
@@ -428,86 +428,69 @@ def _cmax_check(lib, cmax) -> None:
         raise RuntimeError("this GEMM shape does not write chunk maxima (few-row stream kernels only)")
 
 
-def gemm_q4(fmt: int, wq: torch.Tensor, sbuf: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16,
-            bias=None, out: Optional[torch.Tensor] = None, norm: bool = False, eps: float = 1e-6, rope=None,
-            gain: bool = False, cmax: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """GGUF Q4_0 (``fmt`` 0) / Q4_K (1) weight GEMM (``csrc/gemm_q4.hip``; any M: rows beyond the stream kernel's LDS
-    copy run on ``csrc/gemm_qtile.hip``, one pass over the weights per 64 rows, see ``set_q_tile``): y = epi(B(x) @
-    W^T) with W the blocks' exact values and (``wq``, ``sbuf``) = ``models.q4.pack_q4(...)``; ``gain``: the scale
-    buffer ends with the fp32 RMSNorm gain, applied to the activations (``norm`` must be set).  Same epilogues,
-    RMSNorm fusion and ``rope`` arguments as ``gemm_w8``."""
+def _gemm_q(fmt: int, wq, sbuf, x, n: int, epi: int, bias, out, norm: bool, eps: float, rope, gain: bool, cmax,
+            tile0: int, name: str) -> torch.Tensor:
+    """``gemm_q4`` / ``gemm_q6``: the argument checks and the call (``fmt`` 0 Q4_0, 1 Q4_K, 2 Q6_K; ``tile0``: Q6_K)."""
     lib = load()
     _gpu(wq, sbuf, x)
     M, K = x.shape
     assert x.dtype == torch.bfloat16 and x.stride(1) == 1 and M >= 1
     assert wq.dtype == torch.uint8 and wq.shape[0] * 16 == n and wq.shape[1] * 128 == K, (tuple(wq.shape), K, n)
-    sc_bytes, dd_bytes = n * K // 16, (n * K // 64 if fmt == 1 else 0)
+    sc_bytes, dd_bytes = n * K // 16, (n * K // 64 if fmt != 0 else 0)
     assert sbuf.dtype == torch.uint8 and sbuf.numel() == sc_bytes + dd_bytes + (4 * K if gain else 0)
-    n_out = n // 2 if epi in (EPI_SILU, EPI_GELU) else n
+    if fmt == 2:
+        assert epi in (EPI_BF16, EPI_RESID, EPI_F32, EPI_QKV_ROPE), "gemm_q6 has no gate/up activation epilogue"
+    n_out = n // 2 if epi in (EPI_SILU, EPI_GELU) else 16 * tile0 + n
     if epi == EPI_RESID:
         assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
+    if epi == EPI_QKV_ROPE and fmt == 2:
+        assert rope is not None and out is not None, "EPI_QKV_ROPE needs the rope/cache arguments and the q rows"
+    elif epi == EPI_QKV_ROPE:
+        assert rope is not None, "EPI_QKV_ROPE needs the rope/cache arguments"
     if out is None:
         out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
+    elif fmt == 2 and epi != EPI_QKV_ROPE:
+        assert out.shape[1] >= n_out
+    assert fmt != 2 or bias is None or bias.numel() >= n_out
     r = rope or {}
-    if epi == EPI_QKV_ROPE:
-        assert rope is not None, "EPI_QKV_ROPE needs the rope/cache arguments"
     T_max = r["kc"].shape[-2] if rope else 0
     if rope and is_fp8_cache(r["kc"]):
         epi |= EPI_KV_FP8
     base = sbuf.data_ptr()
     _cmax_set(lib, cmax, epi)
-    rc = lib.cain_gemm_q4(int(fmt), _p(wq), base, base + sc_bytes, (base + sc_bytes + dd_bytes) if gain else None,
-                          _p(x), x.stride(0), K, n, M, _p(out), out.stride(0), _p(bias), int(bool(norm)), eps,
-                          _p(r.get("slot")), _p(r.get("pos")), _p(r.get("cos_t")), _p(r.get("sin_t")),
-                          _p(r.get("kc")), _p(r.get("vtc")), r.get("H", 0), r.get("Hkv", 0), r.get("hd", 0), T_max,
-                          epi, _stream())
-    _check(rc, "gemm_q4")
+    args = [int(fmt), _p(wq), base, base + sc_bytes, (base + sc_bytes + dd_bytes) if gain else None, _p(x),
+            x.stride(0), K, n, M, _p(out), out.stride(0), _p(bias), int(bool(norm)), eps, _p(r.get("slot")),
+            _p(r.get("pos")), _p(r.get("cos_t")), _p(r.get("sin_t")), _p(r.get("kc")), _p(r.get("vtc")),
+            r.get("H", 0), r.get("Hkv", 0), r.get("hd", 0), T_max, epi]
+    rc = lib.cain_gemm_q6(*args, int(tile0), _stream()) if fmt == 2 else lib.cain_gemm_q4(*args, _stream())
+    _check(rc, name)
     _cmax_check(lib, cmax)
     return out
+
+
+def gemm_q4(fmt: int, wq: torch.Tensor, sbuf: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16,
+            bias=None, out: Optional[torch.Tensor] = None, norm: bool = False, eps: float = 1e-6, rope=None,
+            gain: bool = False, cmax: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """GGUF Q4_0 (``fmt`` 0) / Q4_K (1) weight GEMM (``csrc/gemm_qstream.hip``; any M: rows beyond the stream kernel's
+    LDS copy run on ``csrc/gemm_qtile.hip``, one pass over the weights per 64 rows, see ``set_q_tile``): y = epi(B(x) @
+    W^T) with W the blocks' exact values and (``wq``, ``sbuf``) = ``models.q4.pack_q4(...)``; ``gain``: the scale
+    buffer ends with the fp32 RMSNorm gain, applied to the activations (``norm`` must be set).  Same epilogues,
+    RMSNorm fusion and ``rope`` arguments as ``gemm_w8``."""
+    assert fmt in (0, 1), fmt
+    return _gemm_q(fmt, wq, sbuf, x, n, epi, bias, out, norm, eps, rope, gain, cmax, 0, "gemm_q4")
 
 
 def gemm_q6(wq: torch.Tensor, sbuf: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16, bias=None,
             out: Optional[torch.Tensor] = None, norm: bool = False, eps: float = 1e-6, rope=None, gain: bool = False,
             cmax: Optional[torch.Tensor] = None, tile0: int = 0) -> torch.Tensor:
-    """GGUF Q6_K weight GEMM (``csrc/gemm_q6.hip``; any M: rows beyond the stream kernel's LDS copy run on
+    """GGUF Q6_K weight GEMM (``csrc/gemm_qstream.hip``; any M: rows beyond the stream kernel's LDS copy run on
     ``csrc/gemm_qtile.hip``, one pass over the weights per 64 rows, see ``set_q_tile``): y = epi(B(x) @ W^T) with
     W the blocks' exact values and (``wq``, ``sbuf``) = ``models.q4.pack_q6(...)``.  Epilogues EPI_BF16 / EPI_RESID
     / EPI_F32 / EPI_QKV_ROPE; ``gain``, ``norm``, ``rope`` and ``cmax`` as ``gemm_q4``.  ``tile0``: the 16-row tile
     the first of the ``n`` weight rows is in the epilogue's eyes -- output columns (``out`` then has at least 16
     tile0 + n), ``bias`` (indexed from row 0 of the whole projection) and, under EPI_QKV_ROPE, the head or V row:
     the V rows of a fused QKV projection run as a launch of their own with ``tile0 = (H + Hkv) hd / 16``."""
-    lib = load()
-    _gpu(wq, sbuf, x)
-    M, K = x.shape
-    assert x.dtype == torch.bfloat16 and x.stride(1) == 1 and M >= 1
-    assert wq.dtype == torch.uint8 and wq.shape[0] * 16 == n and wq.shape[1] * 128 == K, (tuple(wq.shape), K, n)
-    sc_bytes, dd_bytes = n * K // 16, n * K // 64
-    assert sbuf.dtype == torch.uint8 and sbuf.numel() == sc_bytes + dd_bytes + (4 * K if gain else 0)
-    assert epi in (EPI_BF16, EPI_RESID, EPI_F32, EPI_QKV_ROPE), "gemm_q6 has no gate/up activation epilogue"
-    n_out = 16 * tile0 + n
-    if epi == EPI_RESID:
-        assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
-    if epi == EPI_QKV_ROPE:
-        assert rope is not None and out is not None, "EPI_QKV_ROPE needs the rope/cache arguments and the q rows"
-    elif out is None:
-        out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
-    else:
-        assert out.shape[1] >= n_out
-    assert bias is None or bias.numel() >= n_out
-    r = rope or {}
-    T_max = r["kc"].shape[-2] if rope else 0
-    if rope and is_fp8_cache(r["kc"]):
-        epi |= EPI_KV_FP8
-    base = sbuf.data_ptr()
-    _cmax_set(lib, cmax, epi)
-    rc = lib.cain_gemm_q6(2, _p(wq), base, base + sc_bytes, (base + sc_bytes + dd_bytes) if gain else None,
-                          _p(x), x.stride(0), K, n, M, _p(out), out.stride(0), _p(bias), int(bool(norm)), eps,
-                          _p(r.get("slot")), _p(r.get("pos")), _p(r.get("cos_t")), _p(r.get("sin_t")),
-                          _p(r.get("kc")), _p(r.get("vtc")), r.get("H", 0), r.get("Hkv", 0), r.get("hd", 0), T_max,
-                          epi, int(tile0), _stream())
-    _check(rc, "gemm_q6")
-    _cmax_check(lib, cmax)
-    return out
+    return _gemm_q(2, wq, sbuf, x, n, epi, bias, out, norm, eps, rope, gain, cmax, tile0, "gemm_q6")
 
 
 def set_q_tile(mode: int) -> None:

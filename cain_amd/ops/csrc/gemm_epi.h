@@ -210,3 +210,7 @@ __device__ __forceinline__ void epi_cmax(const GemmArgs& a, int gt, int m, int l
   mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
   if ((lane >> 4) == 0 && m < a.M) a.cmax[(size_t)m * a.ld_cm + gt] = mx;
 }
+
+// Host side (gemm.hip): the cmax buffer pending for the next few-row fp32-logits GEMM of N columns, now marked
+// written (null: none pending or N not whole chunks) -- every weight-format entry claims it for its GemmArgs::cmax
+CAIN_API float* cain_gemm_cmax_claim(int N);

@@ -1,16 +1,17 @@
-// Shared by the GGUF weight kernels (gemm_q4.hip, gemm_q6.hip: few-row stream kernels; gemm_qtile.hip: the many-row
-// tile kernels): the formats, the code -> bf16 decodes and the small lane sums.  The packed layouts are in the two
-// stream files' headers (cain_amd/models/q4.py pack_q4 / pack_q6).
+// Shared by the GGUF weight kernels (gemm_qstream.hip: the few-row stream kernels; gemm_qtile.hip: the many-row
+// tile kernels): the formats, the code -> bf16 decodes, the small lane sums and the barrier.  The formats, their
+// arithmetic and the packed layouts are in gemm_qstream.hip's header (cain_amd/models/q4.py pack_q4 / pack_q6).
 #pragma once
 #include "common.h"
 
 enum { Q4F_0 = 0, Q4F_K = 1, Q6F_K = 2 };  // models/q4.py Q4_0, Q4_K, Q6_K
 
-typedef uint32_t q4u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t q4u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t q6u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t q6u32x2 __attribute__((ext_vector_type(2)));
-typedef short q6s16x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t qu32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t qu32x2 __attribute__((ext_vector_type(2)));
+typedef short qs16x4 __attribute__((ext_vector_type(4)));
+
+// workgroup barrier behind this wave's LDS accesses only (global loads stay in flight across it)
+__device__ __forceinline__ void q_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // four codes (one byte lane per k: low nibble k = j, high nibble k = j + 4, j = 0..3) -> bf16 128 + q, k order
 __device__ __forceinline__ bf16x8 q4_frag(uint32_t w) {
@@ -21,7 +22,7 @@ __device__ __forceinline__ bf16x8 q4_frag(uint32_t w) {
   const uint32_t p1 = __builtin_amdgcn_perm(C43, lo, 0x05030402u);  // k2, k3
   const uint32_t p2 = __builtin_amdgcn_perm(C43, hi, 0x05010400u);  // k4, k5
   const uint32_t p3 = __builtin_amdgcn_perm(C43, hi, 0x05030402u);  // k6, k7
-  return __builtin_bit_cast(bf16x8, q4u32x4{p0, p1, p2, p3});
+  return __builtin_bit_cast(bf16x8, qu32x4{p0, p1, p2, p3});
 }
 
 __device__ __forceinline__ float q4_h2f(uint32_t h) { return float(__builtin_bit_cast(_Float16, (uint16_t)h)); }
@@ -35,7 +36,7 @@ __device__ __forceinline__ float q4_quad_sum(float v) {
 }
 
 // the 4 codes of Q6_K MFMA s (bytes j = 0..3 of one low and one high dword) -> bf16 128 + q, k order
-__device__ __forceinline__ q6s16x4 q6_frag(const q6u32x4& lo, const q6u32x2& hi, int s) {
+__device__ __forceinline__ qs16x4 q6_frag(const qu32x4& lo, const qu32x2& hi, int s) {
   const uint32_t l = (lo[s >> 1] >> (4 * (s & 1))) & 0x0f0f0f0fu;
   const int sh = 2 * (s & 3);  // the pair's bit position; it goes to bits 4..5 of its byte
   const uint32_t h = (sh <= 4 ? hi[s >> 2] << (4 - sh) : hi[s >> 2] >> (sh - 4)) & 0x30303030u;
@@ -44,7 +45,7 @@ __device__ __forceinline__ q6s16x4 q6_frag(const q6u32x4& lo, const q6u32x2& hi,
   constexpr uint32_t C43 = 0x43434343u;
   const uint32_t p0 = __builtin_amdgcn_perm(C43, b, 0x05010400u);  // k0, k1
   const uint32_t p1 = __builtin_amdgcn_perm(C43, b, 0x05030402u);  // k2, k3
-  return __builtin_bit_cast(q6s16x4, q6u32x2{p0, p1});
+  return __builtin_bit_cast(qs16x4, qu32x2{p0, p1});
 }
 
 __device__ __forceinline__ float q6_i8f(uint32_t w, int byte) { return float(int(int8_t(w >> (8 * byte)))); }

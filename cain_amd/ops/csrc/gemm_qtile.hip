@@ -1,8 +1,8 @@
 // GGUF Q4_0 / Q4_K / Q6_K weights against up to 64 activation rows per launch: ONE pass over the weight bytes per 64
-// rows (a prefill chunk, a continuous batch), where the stream kernels (gemm_q4.hip, gemm_q6.hip) hold all rows of
+// rows (a prefill chunk, a continuous batch), where the stream kernels (gemm_qstream.hip) hold all rows of
 // the whole K in LDS and so stream the matrix once per 1-16 rows.
 //
-// Arithmetic: the stream kernels', part by part (their headers).  The codes enter the bf16 MFMA unscaled as 128 + q
+// Arithmetic: the stream kernels', part by part (gemm_qstream.hip's header).  The codes enter the bf16 MFMA unscaled as 128 + q
 // (q4_frag / q6_frag), one zero-accumulator MFMA per scale block (16x16x32 per 32-block for Q4, 16x16x16 per
 // 16-group for Q6_K), the block's fp32 scale applied to that fp32 partial, and the correction (128 s + o) X_b
 // (Q4) / 160 s X_g (Q6_K) summed by v_mfma_f32_16x16x4_f32 over the block sums X of the activations.  The RMSNorm
@@ -45,8 +45,6 @@ struct QTArgs {
 
 constexpr int QT_SLAB = 256;       // k per slab
 constexpr int QT_ROW_BYTES = 512;  // one row of a slab in LDS
-
-__device__ __forceinline__ void qt_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <int FMT, int NB, int EPI, bool NORM>
 __device__ __forceinline__ void qtile_body(const GemmArgs& a, const QTArgs& q) {
@@ -119,9 +117,9 @@ __device__ __forceinline__ void qtile_body(const GemmArgs& a, const QTArgs& q) {
 
   // ---- this wave's weights: one item per slab (2 quads of the lane's weight row 16 tile + m16)
   struct Quad {
-    q4u32x4 w;   // Q4: the 32 codes; Q6_K: their low nibbles
-    q4u32x2 hi;  // Q6_K: the high bit pairs
-    q4u32x2 s;   // the quad's block scales (Q4: 4 x 16 bits; Q6_K: 8 x int8)
+    qu32x4 w;   // Q4: the 32 codes; Q6_K: their low nibbles
+    qu32x2 hi;  // Q6_K: the high bit pairs
+    qu32x2 s;   // the quad's block scales (Q4: 4 x 16 bits; Q6_K: 8 x int8)
   };
   struct Item {
     Quad q[2];
@@ -135,13 +133,13 @@ __device__ __forceinline__ void qtile_body(const GemmArgs& a, const QTArgs& q) {
     for (int h = 0; h < 2; ++h) {
       const size_t tq = (size_t)tile * KQ + 2 * j + h;
       if constexpr (Q6) {
-        it.q[h].w = ldw(reinterpret_cast<const q4u32x4*>(wbase + tq * 1536) + lane);
-        it.q[h].hi = ldw(reinterpret_cast<const q4u32x2*>(wbase + tq * 1536 + 1024) + lane);
+        it.q[h].w = ldw(reinterpret_cast<const qu32x4*>(wbase + tq * 1536) + lane);
+        it.q[h].hi = ldw(reinterpret_cast<const qu32x2*>(wbase + tq * 1536 + 1024) + lane);
       } else {
-        it.q[h].w = ldw(reinterpret_cast<const q4u32x4*>(wbase) + tq * 64 + lane);
-        it.q[h].hi = q4u32x2{0u, 0u};
+        it.q[h].w = ldw(reinterpret_cast<const qu32x4*>(wbase) + tq * 64 + lane);
+        it.q[h].hi = qu32x2{0u, 0u};
       }
-      it.q[h].s = ldw(reinterpret_cast<const q4u32x2*>(q.sc) + tq * 16 + m16);
+      it.q[h].s = ldw(reinterpret_cast<const qu32x2*>(q.sc) + tq * 16 + m16);
     }
     if constexpr (FMT == Q4F_0) it.d = 0;
     else it.d = ldw(reinterpret_cast<const uint32_t*>(q.dd) + ((size_t)tile * (KQ >> 1) + j) * 16 + m16);
@@ -211,7 +209,7 @@ __device__ __forceinline__ void qtile_body(const GemmArgs& a, const QTArgs& q) {
         for (int s = 0; s < 8; ++s) sc[s] = d * q6_i8f(qd.s[s >> 2], s & 3);
         // the correction MFMAs' coefficients: groups 8 h + g and 8 h + 4 + g of this lane's weight row
         const float c0 = (160.f * d) * q6_i8f(qd.s[0], g), c1 = (160.f * d) * q6_i8f(qd.s[1], g);
-        q6s16x4 wf[8];
+        qs16x4 wf[8];
 #pragma unroll
         for (int s = 0; s < 8; ++s) wf[s] = q6_frag(qd.w, qd.hi, s);
 #pragma unroll
@@ -219,7 +217,7 @@ __device__ __forceinline__ void qtile_body(const GemmArgs& a, const QTArgs& q) {
           f32x4 t[8];
 #pragma unroll
           for (int s = 0; s < 8; ++s) {  // k = 128 h + 16 s + 4 g: chunk 16 h + 2 s + (g >> 1), its half g & 1
-            const q6s16x4 xv = *reinterpret_cast<const q6s16x4*>(xb + xa[s] + (b * 16 * QT_ROW_BYTES + h * 256));
+            const qs16x4 xv = *reinterpret_cast<const qs16x4*>(xb + xa[s] + (b * 16 * QT_ROW_BYTES + h * 256));
             t[s] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(xv, wf[s], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
           }
           corr[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(sb[sa + (b * 16 * SS + 8 * h)], c0, corr[b], 0, 0, 0);
@@ -241,7 +239,7 @@ __device__ __forceinline__ void qtile_body(const GemmArgs& a, const QTArgs& q) {
   w_load(ring[0], 0);
   x_load(0);
   x_store(0);
-  qt_barrier();
+  q_barrier();
   for (int j0 = 0; j0 < NS; j0 += 2) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -253,7 +251,7 @@ __device__ __forceinline__ void qtile_body(const GemmArgs& a, const QTArgs& q) {
         __builtin_amdgcn_sched_barrier(0);
         step(ring[u], u);
         if (more) x_store(u ^ 1);
-        qt_barrier();  // slab j + 1 is written; every wave is done reading slab j
+        q_barrier();  // slab j + 1 is written; every wave is done reading slab j
       }
     }
   }
@@ -266,7 +264,7 @@ __device__ __forceinline__ void qtile_body(const GemmArgs& a, const QTArgs& q) {
         for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
         if (kc == 0) row_ss[srow + 8 * i] = v;
       }
-    qt_barrier();
+    q_barrier();
   }
 
   // ---- epilogue, per row block: D'[m = 4 g + i][n = m16] through the wave's LDS patch into the epilogues' lane
@@ -317,7 +315,7 @@ static hipError_t qt_launch_nb(int nb, const GemmArgs& a, const QTArgs& q, int g
   const dim3 g(grid), b(256);
   if constexpr (FMT == Q6F_K) {
     if constexpr (EPI == EPI_SILU || EPI == EPI_GELU) {
-      return hipErrorInvalidValue;  // no Q6_K gate/up epilogue (gemm_q6.hip)
+      return hipErrorInvalidValue;  // no Q6_K gate/up epilogue (gemm_qstream.hip)
     } else {
       hipLaunchKernelGGL((q6_tile_kernel<1, EPI, NORM>), g, b, 0, st, a, q);
     }

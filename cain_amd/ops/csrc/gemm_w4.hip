@@ -530,7 +530,6 @@ CAIN_API int cain_gemm_w4_ex(const void* Wp, const void* wsc, const void* X, int
                              int ldy, const float* bias, int norm, float eps, const int* slot, const int* pos,
                              const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
                              int T_max, void* ws, long long ws_bytes, int epi_flags, hipStream_t st);
-CAIN_API float* cain_gemm_cmax_claim(int N);  // gemm.hip
 
 // Same arguments as cain_gemm_w8 (gemm_w8.hip); Wp is the MXFP4 packing, wsc its e8m0 scale bytes.  No workspace:
 // never split (cain_gemm_w4_ex is the engine's entry).

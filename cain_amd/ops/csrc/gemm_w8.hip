@@ -279,8 +279,6 @@ static hipError_t w8_launch_e(int epi, int var, const GemmArgs& a, const float* 
 #undef CAIN_W8_VAR
 }
 
-CAIN_API float* cain_gemm_cmax_claim(int N);  // gemm.hip
-
 // Same arguments as cain_gemm (gemm.hip) plus the per-row weight scales; Wp is the fp8 packing.
 CAIN_API int cain_gemm_w8(const void* Wp, const float* wscale, const void* X, int ldx, int K, int N, int M, void* Y,
                           int ldy, const float* bias, int norm, float eps, const int* slot, const int* pos,

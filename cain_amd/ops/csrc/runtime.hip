@@ -94,7 +94,7 @@ extern "C" {
 // weight storage of a plan (CainPlanDesc::wfmt)
 enum { WFMT_BF16 = 0, WFMT_FP8 = 1, WFMT_FP4 = 2, WFMT_Q4_0 = 3, WFMT_Q4_K = 4 };
 // format of one matrix of a WFMT_Q4_* plan (CainLayer::f*, CainPlanDesc::flm_head): 0 = the plan's wfmt, else
-// WFMT_Q4_0 / WFMT_Q4_K or Q6_K (gemm_q6.hip: a Q4_K_M file's output head, attn_v and ffn_down tensors)
+// WFMT_Q4_0 / WFMT_Q4_K or Q6_K (gemm_qstream.hip: a Q4_K_M file's output head, attn_v and ffn_down tensors)
 enum { MFMT_PLAN = 0, MFMT_Q6_K = 5 };
 
 // RMSNorm gains are folded into the weight columns of the GEMM each norm feeds (attn_norm -> wqkv,
@@ -230,7 +230,7 @@ static int g_w4a8_min_rows = 16;
 // rows a forward of this plan may have: 64 for the few-row-only weight formats
 int max_rows(const CainPlanDesc& d) {
   if ((d.wfmt == WFMT_FP4 || d.wfmt == WFMT_FP8) && !d.x8) return d.Mpad < 64 ? d.Mpad : 64;
-  if (d.wfmt == WFMT_Q4_0 || d.wfmt == WFMT_Q4_K) return d.Mpad < 64 ? d.Mpad : 64;  // 16-row launches (gemm_q4.hip)
+  if (d.wfmt == WFMT_Q4_0 || d.wfmt == WFMT_Q4_K) return d.Mpad < 64 ? d.Mpad : 64;  // 16-row launches (gemm_qstream.hip)
   return d.Mpad < CAIN_MAX_ROWS ? d.Mpad : CAIN_MAX_ROWS;
 }
 
@@ -254,7 +254,7 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
     void* vcm = const_cast<void*>(vc);
     const bool gguf = d.wfmt == WFMT_Q4_0 || d.wfmt == WFMT_Q4_K;
     if (gguf && mf == MFMT_Q6_K) {
-      // Q6_K (gemm_q6.hip): ws = [int8 group scales: N K / 16 bytes][fp32 d: N K / 64 bytes][the fp32 norm gain]
+      // Q6_K (gemm_qstream.hip): ws = [int8 group scales: N K / 16 bytes][fp32 d: N K / 64 bytes][the fp32 norm gain]
       const char* sc = static_cast<const char*>(ws);
       const char* dd = sc + (size_t)N * K / 16;
       const float* gain = d.q4_gain && norm ? reinterpret_cast<const float*>(dd + (size_t)N * K / 64) : nullptr;
@@ -269,7 +269,7 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
                             vcm, d.H, d.Hkv, d.hd, d.T_max, d.gemm_ws, d.gemm_ws_bytes, epi, st);
     }
     if (gguf) {
-      // GGUF Q4_0 / Q4_K (gemm_q4.hip): ws = [block scales: N K / 16 bytes][Q4_K: (d, dmin): N K / 64 bytes]
+      // GGUF Q4_0 / Q4_K (gemm_qstream.hip): ws = [block scales: N K / 16 bytes][Q4_K: (d, dmin): N K / 64 bytes]
       // [the fp32 norm gain over K, when the plan keeps gains unfolded (a GGUF file's exact values)]
       const char* sc = static_cast<const char*>(ws);
       const char* dd = sc + (size_t)N * K / 16;

@@ -10,11 +10,11 @@ int64 product bit for bit, as long as
 because any partial sum, over any subset of k in any order, is bounded by the sum of the absolute products.
 ``Weights.bounds`` lists (B1) and, per format, one matrix per further intermediate a kernel forms:
 
-* Q4_0 / Q4_K (gemm_q4.hip): the codes enter the MFMA as 128 + q, so per weight row the kernel sums
+* Q4_0 / Q4_K (gemm_qstream.hip): the codes enter the MFMA as 128 + q, so per weight row the kernel sums
   ``s_b T_b`` with ``T_b = sum_k x_k (128 + q_k)`` and subtracts ``(128 s_b + o_b) X_b`` with ``X_b = sum_k x_k``
   (s = d, o = 8 d for Q4_0; s = d sc, o = dmin m for Q4_K).  Both sums stay integers below 2^24 when
   ``sum_k |x_k| s (128 + q_k) < 2^24`` and ``sum_k |x_k| (128 s + o) < 2^24``: two more matrices in ``bounds``.
-* Q6_K (gemm_q6.hip): ``s_g T_g`` and ``160 s_g X_g`` with s = d sc (int8): ``|s| (128 + q)`` and ``160 |s|``.
+* Q6_K (gemm_qstream.hip): ``s_g T_g`` and ``160 s_g X_g`` with s = d sc (int8): ``|s| (128 + q)`` and ``160 |s|``.
 * bf16 wide GEMM, variant 0 (wgemm.hip): each k range's partial is stored as fp16 scaled by 2^-ex with
   ex = max(frexp_exp(max |v|) - 14, 0), i.e. unscaled while |v| < 2^14; fp16 holds integers up to 2^11 exactly, so
   every k range needs ``sum_{k in range} |x w| < 2^11`` (``assert_fp16_slabs``; the ranges are ``wide_k_ranges``, the

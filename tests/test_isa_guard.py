@@ -65,7 +65,7 @@ def test_no_split_or_eight_wave_qkv_instance(stream_kernels):
         assert not (epi == 5 and (split or waves == 8)), name
 
 
-# gemm_q4.hip's stream kernels: the same loop, plus the activation-staging loop's gain loads (4 waits)
+# gemm_qstream.hip's Q4 stream kernels: the same loop, plus the activation-staging loop's gain loads (4 waits)
 Q4_LIMIT = {0: 9, 1: 9, 2: 5, 3: 5, 4: 5, 5: 21}
 
 
@@ -76,7 +76,8 @@ def test_q4_stream_kernels_keep_counted_waits():
     found = {}
     for co in isa_guard.code_objects(lib):
         found.update(isa_guard.kernel_loop_waits(isa_guard.disassemble(co), "q4_stream_kernel"))
-    assert len(found) >= 20
+    # ({4, 8} waves x 5 epilogues + the 4-wave QKV) x 2 norms x 2 formats
+    assert len(found) == 44, sorted(found)
     for name, (n_loop, waits) in found.items():
         m = re.search(r"q4_stream_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)ELi(\d)E", name)
         waves, u, epi, norm, fmt = (int(x) for x in m.groups())

@@ -1,5 +1,5 @@
-"""gemm_q6.hip's stream kernels keep their counted load waits in the BUILT library (CPU-only check), as
-tests/test_isa_guard.py holds gemm_q4.hip's to: every q6_stream_kernel instance has a loop, and at most Q4_LIMIT[epi]
+"""gemm_qstream.hip's Q6_K stream kernels keep their counted load waits in the BUILT library (CPU-only check), as
+tests/test_isa_guard.py holds its Q4 instances to: every q6_stream_kernel instance has a loop, and at most Q4_LIMIT[epi]
 ``s_waitcnt vmcnt(0)`` in its loops -- the project's bound for the same loop shape (the ring, the activation
 staging's gain loads, the epilogue's loads at a tile edge).  Only wait counts are read."""
 import re

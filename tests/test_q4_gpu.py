@@ -1,4 +1,4 @@
-"""GGUF Q4_0 / Q4_K weight kernels of ``csrc/gemm_q4.hip`` against a plain PyTorch fp32 reference on the blocks'
+"""GGUF Q4_0 / Q4_K weight kernels of ``csrc/gemm_qstream.hip`` against a plain PyTorch fp32 reference on the blocks'
 values as llama.cpp decodes them (``gguf.py``'s decoders: the fp32 dequantised oracle), every epilogue, the fused
 RMSNorm with and without a separate gain, multi-launch row counts, and the ``weight_dtype="q4_0" / "q4_k"`` engine
 against the torch oracle on the same dequantised weights."""

@@ -1,4 +1,4 @@
-"""GGUF Q4_0 / Q4_K blocks for the native Q4 kernel (models/q4.py, ops/csrc/gemm_q4.hip), CPU checks: the block
+"""GGUF Q4_0 / Q4_K blocks for the native Q4 kernel (models/q4.py, ops/csrc/gemm_qstream.hip), CPU checks: the block
 quantisers write ggml's layouts (Q4_0 byte-identical to the numpy reference quantiser), the field extraction is
 bit-exact against gguf.py's decoders, and an emulation of the kernel's arithmetic on the PACKED bytes -- its lane
 layout, nibble order and scale indexing, T_b = sum x (128 + q) and the (128 s + o) X_b correction -- reproduces the
@@ -47,7 +47,7 @@ def test_fields_are_exact(fmt):
 
 
 def emulate(wq, sbuf, fmt, x, n, k):
-    """The kernel's arithmetic on the packed bytes (gemm_q4.hip step): per 128-k quad p, MFMA s (block 4p + s) and
+    """The kernel's arithmetic on the packed bytes (gemm_qstream.hip step): per 128-k quad p, MFMA s (block 4p + s) and
     lane group g the codes of k = 128p + 32s + 8g + j come from dword s, byte j & 3, nibble j >> 2; T = sum x (128 +
     q); out = sum_b s_b T_b - (128 s_b + o_b) X_b with the scales read at the kernel's offsets."""
     nt, kq = n // 16, k // 128

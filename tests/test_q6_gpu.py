@@ -1,4 +1,4 @@
-"""The GGUF Q6_K weight kernel of ``csrc/gemm_q6.hip`` against a plain PyTorch fp32 reference on the blocks' values
+"""The GGUF Q6_K weight kernel of ``csrc/gemm_qstream.hip`` against a plain PyTorch fp32 reference on the blocks' values
 as ``gguf.py``'s ``_q6_k`` decodes them, its epilogues and the fused RMSNorm with and without a separate gain, the V
 rows of a QKV projection as a launch of their own behind a Q4_K launch of the q / k rows, and the engine on the
 Q4_K_M mix: ``weight_dtype="q4_k_m"`` against the torch oracle on per-matrix round trips, and a Q4_K_M GGUF file

@@ -1,4 +1,4 @@
-"""GGUF Q6_K blocks for the native Q6_K kernel (models/q4.py, ops/csrc/gemm_q6.hip) and the Q4_K_M mix, CPU checks:
+"""GGUF Q6_K blocks for the native Q6_K kernel (models/q4.py, ops/csrc/gemm_qstream.hip) and the Q4_K_M mix, CPU checks:
 the field extraction is bit-exact against gguf.py's ``_q6_k`` decoder on random block bytes, an emulation of the
 kernel's arithmetic on the PACKED bytes -- its lane layout, nibble / bit-pair order and scale indexing, T_g = sum x
 (128 + q) and the 160 s_g X_g correction -- reproduces the fp32 product with the decoded weights, a Q4_K_M file goes
@@ -49,7 +49,7 @@ def test_fields_are_exact_on_random_block_bytes():
 
 
 def emulate(wq, sbuf, x, n, k, dt=torch.float32):
-    """gemm_q6.hip's step on the packed bytes: per (tile t, quad p) the lane 16 g + r reads 16 bytes of low nibbles
+    """gemm_qstream.hip's step on the packed bytes: per (tile t, quad p) the lane 16 g + r reads 16 bytes of low nibbles
     at 16 lane and 8 bytes of high bit pairs at 1024 + 8 lane; MFMA s takes k = 128 p + 16 s + 4 g + j from byte j of
     low dword s >> 1 (nibble s & 1) and of high dword s >> 2 (bits 2 (s & 3)); T = sum x (128 + q); out = sum_g s_g
     T_g - 160 s_g X_g with s_g = d sc_g read at the kernel's offsets."""

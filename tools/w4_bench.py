@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """In-graph microbenchmark of the few-row weight-streaming GEMMs: MXFP4 (gemm_w4.hip, every kernel shape), GGUF
-Q4_0 / Q4_K (gemm_q4.hip) and Q6_K (gemm_q6.hip; --dtypes q4_k,q6_k), fp8 (gemm_w8.hip) and bf16 (gemm.hip) on a
+Q4_0 / Q4_K and Q6_K (gemm_qstream.hip; --dtypes q4_k,q6_k), fp8 (gemm_w8.hip) and bf16 (gemm.hip) on a
 model's projection shapes at one row.
 
 Each case captures `reps` calls into one hipGraph (torch.cuda.CUDAGraph) rotating over enough weight copies to
@@ -180,7 +180,7 @@ def main() -> int:
                 q_time(fn, dt, role, N, K, wbytes, fmt, epi)
             elif dt == "q6_k":
                 if epi in (ops.EPI_SILU, ops.EPI_GELU):
-                    continue  # gemm_q6.hip has no gate/up activation epilogue
+                    continue  # Q6_K has no gate/up activation epilogue (gemm_qstream.hip)
                 if role not in ("down", "lm_head") and not ns.q6_everywhere:
                     continue  # a Q4_K_M file keeps these matrices in Q4_K (of QKV only the V rows are Q6_K)
                 # random codes, int8 group scales 1 and d = 2^-5: finite values
