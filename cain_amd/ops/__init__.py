@@ -254,8 +254,8 @@ def set_wide_gemm_variant(v: int) -> None:
 
 
 def set_wide_gemm_inline(mode: int) -> None:
-    """Split-K combine of the wide GEMM (csrc/wgemm.hip wg_inline_combine): 1 inside the GEMM launch (default),
-    0 a separate wgemm_reduce_kernel launch, 2 inside the launch with partners that never wait (tests)."""
+    """Split-K combine of the wide GEMM (csrc/wgemm.hip wg_inline_combine): 0 a separate wgemm_reduce_kernel launch (default),
+    1 inside the GEMM launch (A/B runs), 2 inside the launch with partners that never wait (tests)."""
     load().cain_wgemm_set_inline(int(mode))
 
 

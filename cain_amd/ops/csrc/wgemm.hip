@@ -37,16 +37,14 @@
 //     fragment, split between the WN waves that read the same rows.
 //
 // Split-K: narrow outputs (QKV, O, down: 32-48 column tiles) split K over ks workgroups so ~256 workgroups
-// stream; each writes its tile to a workspace slab (plain stores, fp16: OPT bit 32 below; the sums stay fp32) and
+// stream; each writes its tile to a workspace slab (plain stores, fp16: H16 below; the sums stay fp32) and
 // `wgemm_reduce_kernel` -- the next launch on the stream, so the kernel boundary orders the hand-off -- sums the
-// slabs in fp32 and runs the fused epilogue.  With ks = 1 (gate/up, LM head) the GEMM kernel runs the epilogue itself.  The epilogues are
-// gemm_epi.h's (residual, bias, SiLU/GeLU x up, RoPE + KV-cache append, fp32 logits).
-#include <algorithm>
-#include <cstdlib>
-#include <type_traits>
-
-#include "common.h"
-#include "gemm_epi.h"
+// slabs in fp32 and runs the fused epilogue.  With ks = 1 (gate/up, LM head) the GEMM kernel runs the epilogue
+// itself.  The epilogues are gemm_epi.h's (residual, bias, SiLU/GeLU x up, RoPE + KV-cache append, fp32 logits).
+//
+// The ring loader, the fp16 slab store, the split rule and the launch switches are wgemm_ring.h's, shared with the
+// fp8 / fp4 kernel (wgemm8.hip); this file keeps the bf16 compute loop, the fused RMSNorm, the ks = 1 epilogue, the
+// combine of one unit (wg_reduce_unit: the reduce kernel and the in-launch combine) and the plans.
 #include "wgemm_ring.h"
 
 using namespace wg;
@@ -69,18 +67,24 @@ constexpr int WG_CTR_BYTES = 16 * 1024;  // the workspace region before the slab
 // DMA.  Results are garbage in both.  3 = the full kernel plus timestamps (tools/wgemm_trace.py): lane 0 of wave 0
 // (compute) and of the first loader wave store s_memrealtime / s_memtime at fixed points to w.stamps.
 //
-// H16: split-K slabs in fp16 instead of fp32 (wgemm_reduce_kernel H16 = true reads them): half the slab bytes
-// stored, written back at the kernel boundary (MI355X_MICROARCH.md 'boundary': + dirty bytes / 6 TB/s) and read by
-// the reduce.  Each lane's partials (one activation row) are stored scaled -- NORM: by rsqrt of the row's split sum
-// of squares, else by a power of two -- so rows of outliers keep fp16's relative precision (the reduce sums in
-// fp32); tests/test_wgemm_gpu.py compares them with fp32 slabs on such rows.  (Round 3's loader alternatives -- loader-wave sums of squares, W-only / X-only
-// loader roles, rotated k start, non-temporal X, stage-ordered prologue -- and the in-launch split-K combine all
-// measured within box-to-box noise or slower, profiles/r3/README.md, and were removed.)
-template <int BM, int EPI, bool NORM, bool H16, bool COH>
-__device__ __forceinline__ void wg_reduce_unit(const GemmArgs& a, const WgArgs& w, int unit, int n_units, int lane,
-                                               int ks);
+// Slabs (WgSlab): fp16 instead of fp32 (H16) is half the slab bytes stored, written back at the kernel
+// boundary (MI355X_MICROARCH.md 'boundary': + dirty bytes / 6 TB/s) and read by the reduce.  Each lane's partials
+// (one activation row) are stored scaled -- NORM: by rsqrt of the row's split sum of squares, else by a power of
+// two -- so rows of outliers keep fp16's relative precision (the reduce sums in fp32); tests/test_wgemm_gpu.py
+// compares them with fp32 slabs on such rows.  (Round 3's loader alternatives -- loader-wave sums of squares,
+// W-only / X-only loader roles, rotated k start, non-temporal X, stage-ordered prologue -- measured within
+// box-to-box noise or slower, profiles/r3/README.md, and were removed.  The in-launch split-K combine, INL below,
+// measured slower too; it is still here, off by default: cain_wgemm_set_inline.)
+enum WgSlab {
+  WG_SLAB_F32,        // fp32 partials
+  WG_SLAB_F16_RSQRT,  // fp16, each lane's row scaled by rsqrt of its split sum of squares (part_ss; NORM)
+  WG_SLAB_F16_EXP,    // fp16, each lane scaled by a power of two (part_ex)
+};
+constexpr int wg_slab_mode(bool norm, bool h16) {
+  return !h16 ? WG_SLAB_F32 : norm ? WG_SLAB_F16_RSQRT : WG_SLAB_F16_EXP;
+}
 
-template <int BM, int EPI, bool NORM, bool H16>
+template <int BM, int EPI, bool NORM, int SLAB>
 __device__ void wg_inline_combine(const GemmArgs& a, const WgArgs& w, int blk, int kc, int n_units, int nthr,
                                   unsigned* flags);
 
@@ -88,26 +92,14 @@ __device__ void wg_inline_combine(const GemmArgs& a, const WgArgs& w, int blk, i
 template <int BM, int DX, int DW, int EPI, bool NORM, int NDMA, int ABL = 0, bool H16 = false, bool INL = false>
 __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(const GemmArgs a, const WgArgs w) {
   using G = WgGeo<BM>;
-  constexpr bool MSQ = NORM;                        // MFMA X X^T sums of squares
-  constexpr int NX = DX + 1, NW = DW + 1;
-  constexpr int NLOAD = NDMA ? NDMA : 8;            // waves issuing LDS-DMA
-  constexpr int NWL = NLOAD;                        // waves issuing W pieces
-  constexpr int NXL = NLOAD;                        // waves issuing X pieces
-  constexpr int WPW = 16 / NWL;                     // W blocks (1 KiB) per W-loader wave per stage
-  constexpr int XPW = (BM / 8) / NXL;               // X row octets per X-loader wave per stage
+  using Ring = RingLoader<BM, DX, DW, NDMA, 16, G::W_BYTES, 0, ABL != 2>;
   constexpr int NTHR = 64 * (8 + NDMA);
-  static_assert(DW >= DX && DX >= 1, "W is issued no later than X of the same stage");
-  static_assert(WPW * NWL == 16 && XPW * NXL == BM / 8, "loader split");
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // the one LDS array: [NW W slots][NX X slots]
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // the one LDS array: [DW + 1 W slots][DX + 1 X slots]
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const bool compute = wave < 8;
-  const bool loader = NDMA ? !compute : true;
-  const int lw = NDMA ? wave - 8 : wave;  // loader index
-  const bool wload = loader, xload = loader;
-  const int xl = lw;  // X-loader index
   const int wm = wave % G::WM, wn = (wave / G::WM) % G::WN;
-  const int KS = a.K >> 5, ntiles = a.N >> 4;
+  const int ntiles = a.N >> 4;
   const int nblk = (ntiles + WG_NT - 1) / WG_NT;
   // ABL 3: slots 0/1 start (realtime / memtime), 2 stage 0 ready, 3 stage nst/2 ready, 4 loop end, 5 slab stores
   // drained, 6/7 end (realtime / memtime)
@@ -125,70 +117,13 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
   // and b + 8 share an XCD under round-robin dispatch); the default xcd_blk placement keeps a column block's
   // split partners together instead, for the reduce (wgemm_dispatch).  Speed only, any placement is correct.
   int blk, kc;
-  {
-    wg_block_of(blockIdx.x, w.ks, nblk, w.xcd_blk, blk, kc);
-  }
+  wg_block_of(blockIdx.x, w.ks, nblk, w.xcd_blk, blk, kc);
   const int tile0 = blk * WG_NT;
   const int st0 = kc * w.kst;                    // first stage (64-deep k-step) of this split
   const int nst = min(w.kst, (a.K >> 6) - st0);  // stages of this split
-  auto kstage = [&](int t) { return t; };  // ring stage t -> stage of this split's k range
-
-  // ---- LDS-DMA sources of this loader (per stage: WPW W blocks + XPW X row-octets)
-  // W block j of loader lw: tile (lw * WPW + j) / 2, slice (lw * WPW + j) & 1 (a tile's two slices are 2 KiB
-  // contiguous in the packing); LDS W image: block (tile * 2 + slice) at 1 KiB each
-  const char* wsrc[WPW];
-#pragma unroll
-  for (int j = 0; j < WPW; ++j) {
-    const int q = lw * WPW + j, tn = q >> 1, sl = q & 1;
-    wsrc[j] = reinterpret_cast<const char*>(a.Wp) +
-              ((size_t)min(tile0 + tn, ntiles - 1) * KS + (size_t)st0 * 2 + sl) * 1024 + lane * 16;
-  }
-  // X: octet i covers rows 8i .. 8i + 7; lane -> row 8i + (lane >> 3), LDS slot lane & 7 holding global piece
-  // (lane & 7) ^ ((r >> 1) & 7) (the read side's XOR swizzle)
-  const char* xsrc[XPW];
-#pragma unroll
-  for (int j = 0; j < XPW; ++j) {
-    const int i = xl + NXL * j;
-    const int r = 8 * i + (lane >> 3);
-    const int p = (lane & 7) ^ ((r >> 1) & 7);
-    xsrc[j] = reinterpret_cast<const char*>(a.X) + ((size_t)min(r, a.M - 1) * a.ldx + (size_t)st0 * WG_BK + p * 8) * 2;
-  }
-  char* const xring = smem + NW * G::W_BYTES;
-  auto issue_w = [&](int t) {  // W stage t (relative to st0) into W slot t % NW
-    if constexpr (ABL == 2) return;
-    if (!wload) return;
-    char* base = smem + (t % NW) * G::W_BYTES;
-    const size_t off = (size_t)kstage(t) * 2048;
-#pragma unroll
-    for (int j = 0; j < WPW; ++j) glds16(wsrc[j] + off, base + (lw * WPW + j) * 1024, 1);
-  };
-  auto issue_x = [&](int t) {  // X stage t into X slot t % NX
-    if constexpr (ABL == 2) return;
-    if (!xload) return;
-    char* base = xring + (t % NX) * G::X_BYTES;
-    const size_t off = (size_t)kstage(t) * (WG_BK * 2);
-#pragma unroll
-    for (int j = 0; j < XPW; ++j) glds16(xsrc[j] + off, base + (xl + NXL * j) * 1024, 0);
-  };
-  // issue order: step u (u < 0: prologue) issues W(u + DW), then X(u + DX); so W(t) is always older than X(t) and
-  // waiting for X(t) covers both (vmcnt retires in issue order).  Loads younger than X(t): steps t-DX+1 .. t-1.
-  auto younger_than = [&](int t) {
-    int n = 0;
-#pragma unroll
-    for (int u = t - DX + 1; u < t; ++u) n += WPW * (u + DW < nst) + XPW * (u + DX < nst);
-    return n;
-  };
-  auto land = [&](int t) {  // this loader's pieces of stage t have landed (a loader's own counted wait)
-    if constexpr (ABL != 2) {
-      if (loader) wait_vmcnt_rt(younger_than(t));
-    }
-  };
-  auto issue_step = [&](int t) {
-    if (loader) {
-      if (t + DW < nst) issue_w(t + DW);
-      if (t + DX < nst) issue_x(t + DX);
-    }
-  };
+  // W: 16-row x 32-k blocks, K / 32 per tile, two per stage; X: bf16 rows of ldx elements
+  const Ring ring(smem, wave, lane, a.Wp, a.K >> 5, st0 * 2, reinterpret_cast<const char*>(a.X) + (size_t)st0 * 128,
+                  (size_t)a.ldx * 2, a.M, ntiles, tile0, nst);
 
   // ---- fragment read offsets inside a stage (compute waves)
   const int c = lane & 15, g = lane >> 4;
@@ -210,8 +145,8 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
   for (int mb = 0; mb < G::MB; ++mb) ssq[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   auto read_slice = [&](int t, int s, bf16x8 (&af)[G::TN], bf16x8 (&bfr)[G::MB]) {
-    const char* wbase = smem + (t % NW) * G::W_BYTES + s * 1024;
-    const char* xbase = xring + (t % NX) * G::X_BYTES + xrow0 + xoff[s];
+    const char* wbase = ring.w_slot(t) + s * 1024;
+    const char* xbase = ring.x_slot(t) + xrow0 + xoff[s];
 #pragma unroll
     for (int tn = 0; tn < G::TN; ++tn) af[tn] = *reinterpret_cast<const bf16x8*>(wbase + woff[tn]);
 #pragma unroll
@@ -231,7 +166,7 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-    if constexpr (MSQ) {
+    if constexpr (NORM) {
       if (wn == s) {
 #pragma unroll
         for (int mb = 0; mb < G::MB; ++mb)
@@ -239,37 +174,22 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
       }
     }
   };
-  // ---- prologue: steps -DW .. -1
-  if (loader) {
-#pragma unroll
-    for (int u = -DW; u < 0; ++u) {
-      if (u + DW < nst) issue_w(u + DW);
-      if (u + DX >= 0 && u + DX < nst) issue_x(u + DX);
-    }
-  }
-
   // ---- main loop: nst barriers for every wave; the barrier of stage t + 1 retires stage t's slots, which take
   // the loads of step t + 1 (every wave's reads of stage t completed: lgkmcnt(0) in ring_barrier)
   if (NDMA && !compute) {
-    for (int t = 0; t < nst; ++t) {
-      land(t);
-      ring_barrier();
+    ring.loader_loop([&](int t) {
       if (t == 0) stamp(2, false);
       if (t == nst / 2) stamp(3, false);
-      issue_step(t);
-    }
+    });
   } else if constexpr (ABL == 1) {
-    for (int t = 0; t < nst; ++t) {
-      land(t);
-      ring_barrier();
-      issue_step(t);
-    }
+    ring.loader_loop();
   } else {
     bf16x8 a0[G::TN], b0[G::MB], a1[G::TN], b1[G::MB];
-    land(0);
+    if constexpr (!NDMA) ring.prologue();
+    ring.land(0);
     ring_barrier();
     stamp(2, false);
-    if constexpr (!NDMA) issue_step(0);
+    if constexpr (!NDMA) ring.issue_step(0);
     read_slice(0, 0, a0, b0);
     for (int t = 0; t < nst; ++t) {
       __builtin_amdgcn_sched_barrier(0);
@@ -277,10 +197,10 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
       __builtin_amdgcn_sched_barrier(0);
       const bool more = t + 1 < nst;
       if (more) {
-        land(t + 1);
+        ring.land(t + 1);
         ring_barrier();
         if (t + 1 == nst / 2) stamp(3, false);
-        if constexpr (!NDMA) issue_step(t + 1);
+        if constexpr (!NDMA) ring.issue_step(t + 1);
       }
       __builtin_amdgcn_sched_barrier(0);
       // the next stage's slice-0 reads go in after slice 1's first MFMA: issued before it, they made the
@@ -297,7 +217,7 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
   // ---- per-row sums of squares: the diagonal of each X X^T block (lane (c, g) holds C[4g + i][c], so the
   // diagonal element of row c sits in lane c + 16 * (c >> 2), register c & 3)
   float* s_ss = reinterpret_cast<float*>(smem);  // [2][BM]
-  if constexpr (MSQ) {
+  if constexpr (NORM) {
     if (compute && wn < 2 && (c >> 2) == g) {
 #pragma unroll
       for (int mb = 0; mb < G::MB; ++mb) s_ss[wn * BM + (wm * G::MB + mb) * 16 + c] = ssq[mb][c & 3];
@@ -306,49 +226,44 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
   }
 
   if (w.ks > 1) {
-    // fp32 slab of this split (unit (gt, rb) = 16 x 16 outputs, lane-major f32x4: the reducer's layout) and this
-    // split's per-row sums of squares.
+    // this split's slab (unit (gt, rb) = 16 x 16 outputs, lane-major: the reducer's layout) and per-row sums of
+    // squares; wgemm_reduce_kernel, the next launch on the stream, combines them
     const int n_units = nblk * WG_NT * G::RB;
-    // wgemm_reduce_kernel, the next launch on the stream, combines them
     if (compute) {
       float rs[G::MB];  // NORM: 1 / sqrt(the lane's row sum of squares over this split)
 #pragma unroll
       for (int mb = 0; mb < G::MB; ++mb) {
         const int m = (wm * G::MB + mb) * 16 + c;
-        rs[mb] = MSQ ? __builtin_amdgcn_rsqf(s_ss[m] + s_ss[BM + m] + 1e-30f) : 1.f;
+        rs[mb] = NORM ? __builtin_amdgcn_rsqf(s_ss[m] + s_ss[BM + m] + 1e-30f) : 1.f;
       }
 #pragma unroll
       for (int tn = 0; tn < G::TN; ++tn)
 #pragma unroll
         for (int mb = 0; mb < G::MB; ++mb) {
           const int unit = (tile0 + wn * G::TN + tn) * G::RB + wm * G::MB + mb;
-          const size_t e = ((size_t)kc * n_units + unit) * 64 + lane;
+          const size_t e = wg_slab_at(kc, n_units, unit, lane);
           if constexpr (H16) {
             // fp16 partials scaled per activation row (each lane holds one row m of the unit): NORM shapes by
             // rsqrt of the row's split sum of squares (|partial| <= sqrt(ss) * |W row|, so a row of residual-stream
             // outliers stores weight-sized values), the others by a power of two keeping the lane's largest
             // partial < 2^14 (exponent byte per lane in part_ex); the reducer multiplies back -- no cross-lane work
             // (tests/test_wgemm_gpu.py test_fp16_slabs_scale_outlier_rows; costs, profiles/r4/README.md)
-            const f32x4 v = acc[tn][mb];
-            f32x4 sv;
-            if constexpr (MSQ) {
-              sv = v * rs[mb];
-            } else {
-              const float mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
-              const int ex = max(__builtin_amdgcn_frexp_expf(mx) - 14, 0);  // mx < 2^(ex + 14)
+            wg_store_slab16<INL>(w.part, e, acc[tn][mb], [&](const f32x4& v) {
+              if constexpr (NORM) {
+                return v * rs[mb];
+              } else {
+                const float mx = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                const int ex = max(__builtin_amdgcn_frexp_expf(mx) - 14, 0);  // mx < 2^(ex + 14)
+                f32x4 sv;
 #pragma unroll
-              for (int i = 0; i < 4; ++i) sv[i] = __builtin_amdgcn_ldexpf(v[i], -ex);
-              if constexpr (INL) __hip_atomic_store(w.part_ex + e, (uint8_t)ex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              else w.part_ex[e] = (uint8_t)ex;
-            }
-            f16x4 h;  // (the clamp only bites on non-finite partials)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) h[i] = (_Float16)fminf(fmaxf(sv[i], -65504.f), 65504.f);
-            if constexpr (INL)  // write-through: read by the partners' combine in this launch
-              __hip_atomic_store(reinterpret_cast<uint64_t*>(w.part) + e, __builtin_bit_cast(uint64_t, h),
-                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else
-              reinterpret_cast<f16x4*>(w.part)[e] = h;
+                for (int i = 0; i < 4; ++i) sv[i] = __builtin_amdgcn_ldexpf(v[i], -ex);
+                if constexpr (INL)
+                  __hip_atomic_store(w.part_ex + e, (uint8_t)ex, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                else
+                  w.part_ex[e] = (uint8_t)ex;
+                return sv;
+              }
+            });
           } else if constexpr (INL) {
             const f32x4 v = acc[tn][mb];
             uint64_t* d = reinterpret_cast<uint64_t*>(reinterpret_cast<f32x4*>(w.part) + e);
@@ -371,8 +286,8 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
     if constexpr (INL) {
       // two words of the (drained) ring past the row sums: the kernel's LDS is all dynamic, sized to 160 KiB, so
       // a static __shared__ here would not fit
-      wg_inline_combine<BM, EPI, NORM, H16>(a, w, blk, kc, nblk * WG_NT * G::RB, NTHR,
-                                            reinterpret_cast<unsigned*>(smem + 2 * BM * sizeof(float)));
+      unsigned* flags = reinterpret_cast<unsigned*>(smem + 2 * BM * sizeof(float));
+      wg_inline_combine<BM, EPI, NORM, wg_slab_mode(NORM, H16)>(a, w, blk, kc, n_units, NTHR, flags);
       return;
     }
     if constexpr (ABL == 3) {
@@ -397,8 +312,7 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
     const int gt = tile0 + wn * G::TN + tn;
 #pragma unroll
     for (int mb = 0; mb < G::MB; ++mb) {
-      const int rb = wm * G::MB + mb;
-      const int m = rb * 16 + c;
+      const int m = (wm * G::MB + mb) * 16 + c;
       f32x4 v = acc[tn][mb];
       if constexpr (NORM) v *= rn[mb];
       // the pair epilogues read the partner rows (+8 of the tile) from lane + 32: exchanged by every lane
@@ -429,28 +343,20 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm_kernel(
   }
 }
 
-// Split-K combine + fused epilogue: one wave per 16 x 16 output unit.  The kernel is a few dependent memory
-// round trips long, so every load goes out before the first add: the epilogue inputs (residual row, RoPE position
-// and then its cos / sin) first, then all KS slab pieces and row sums (KS a compile-time split count; KS = 0 is
-// the runtime-count fallback).  Issued after the sum, as before, the epilogue loads were one more round trip
-// (two for QKV: position, then the tables).
-template <int BM, int EPI, bool NORM, int KS, bool H16 = false>
-__global__ __launch_bounds__(256) void wgemm_reduce_kernel(const GemmArgs a, const WgArgs w, int n_units) {
-  const int lane = threadIdx.x & 63;
-  // this workgroup's 4 units on the XCD that wrote their column block's slabs (wg_block_of; w.bnt tiles per block)
-  const int unit = wg_reduce_block(blockIdx.x, w.bnt * (BM / 16) / 4, w.xcd_blk) * 4 + (threadIdx.x >> 6);
-  if (unit >= n_units) return;
-  wg_reduce_unit<BM, EPI, NORM, H16, false>(a, w, unit, n_units, lane, KS ? KS : w.ks);
-}
-
-// One unit's combine: the ks slab pieces (+ row sums / exponents), the epilogue.  COH: the slabs were published
+// One unit's split-K combine + fused epilogue.  The combine is a few dependent memory round trips long, so every
+// load goes out before the first add: the epilogue inputs (residual row, RoPE position and then its cos / sin)
+// first, then the slab pieces (+ row sums / exponents), up to WG_INL_KS of them (more in a second pass), summed in
+// fp32 from piece 0 up.  COH: the slabs were published
 // write-through by partners still running in this launch -- read them with agent-scope loads (past this CU's L1),
-// as the W4 split-K and the attention merge do.  Up to WG_INL_KS pieces are loaded before the first add.
+// as the W4 split-K and the attention merge do.
 constexpr int WG_INL_KS = 8;
-template <int BM, int EPI, bool NORM, bool H16, bool COH>
+template <int BM, int EPI, bool NORM, int SLAB, bool COH>
 __device__ __forceinline__ void wg_reduce_unit(const GemmArgs& a, const WgArgs& w, int unit, int n_units, int lane,
                                                int ks) {
+  static_assert(SLAB == WG_SLAB_F32 || NORM == (SLAB == WG_SLAB_F16_RSQRT), "slab mode");
+  constexpr bool H16 = SLAB != WG_SLAB_F32;
   constexpr int RB = BM / 16;
+  constexpr int NP = WG_INL_KS;  // pieces per pass
   const int gt = unit / RB, rb = unit - gt * RB;
   const int ntiles = a.N >> 4;
   const int m = rb * 16 + (lane & 15);
@@ -476,13 +382,13 @@ __device__ __forceinline__ void wg_reduce_unit(const GemmArgs& a, const WgArgs& 
       return *q;
     }
   };
-  const uint8_t* exsrc = w.part_ex + (size_t)unit * 64 + lane;  // H16 without NORM: the lane's exponent per split
+  const uint8_t* exsrc = w.part_ex + (size_t)unit * 64 + lane;  // WG_SLAB_F16_EXP: the lane's exponent per split
   auto ld_ex = [&](int k) -> int {
     const uint8_t* q = exsrc + (size_t)k * n_units * 64;
     if constexpr (COH) return __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else return *q;
   };
-  const float* ssrc = w.part_ss + (size_t)(gt / w.bnt) * ks * BM + m;
+  const float* ssrc = w.part_ss + (size_t)(gt / WG_NT) * ks * BM + m;
   auto ld_ss = [&](int k) -> float {
     if constexpr (COH) return __hip_atomic_load(ssrc + k * BM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else return ssrc[k * BM];
@@ -494,28 +400,27 @@ __device__ __forceinline__ void wg_reduce_unit(const GemmArgs& a, const WgArgs& 
   };
   f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
   float ss = 0.f;
-  f32x4 p[WG_INL_KS];
-  float q[WG_INL_KS];
-  int ex[WG_INL_KS];
-  // every piece's loads before the first add (up to WG_INL_KS; more pieces in a second pass).  No branch around a
-  // load: past the last piece a lane re-loads the last one (a cache hit) and adds it times 0 -- a conditional load
-  // made hipcc wait for each one (vmcnt(0) per piece: one memory round trip per piece)
-  for (int k0 = 0; k0 < ks; k0 += WG_INL_KS) {
+  f32x4 p[NP];
+  float q[NP];
+  int ex[NP];
+  // No branch around a load: past the last piece a lane re-loads the last one (a cache hit) and adds it times 0 --
+  // a conditional load made hipcc wait for each one (vmcnt(0) per piece: one memory round trip per piece)
+  for (int k0 = 0; k0 < ks; k0 += NP) {
 #pragma unroll
-    for (int k = 0; k < WG_INL_KS; ++k) p[k] = ld_slab(min(k0 + k, ks - 1));
-    if constexpr (H16 && !NORM) {
+    for (int k = 0; k < NP; ++k) p[k] = ld_slab(min(k0 + k, ks - 1));
+    if constexpr (SLAB == WG_SLAB_F16_EXP) {
 #pragma unroll
-      for (int k = 0; k < WG_INL_KS; ++k) ex[k] = ld_ex(min(k0 + k, ks - 1));
+      for (int k = 0; k < NP; ++k) ex[k] = ld_ex(min(k0 + k, ks - 1));
     }
     if constexpr (NORM) {
 #pragma unroll
-      for (int k = 0; k < WG_INL_KS; ++k) q[k] = ld_ss(min(k0 + k, ks - 1));
+      for (int k = 0; k < NP; ++k) q[k] = ld_ss(min(k0 + k, ks - 1));
     }
 #pragma unroll
-    for (int k = 0; k < WG_INL_KS; ++k) {
+    for (int k = 0; k < NP; ++k) {
       const float on = k0 + k < ks ? 1.f : 0.f;
-      if constexpr (H16 && NORM) v += p[k] * (__builtin_sqrtf(q[k] + 1e-30f) * on);
-      else if constexpr (H16) v += unscale(p[k], ex[k]) * on;
+      if constexpr (SLAB == WG_SLAB_F16_RSQRT) v += p[k] * (__builtin_sqrtf(q[k] + 1e-30f) * on);
+      else if constexpr (SLAB == WG_SLAB_F16_EXP) v += unscale(p[k], ex[k]) * on;
       else v += p[k] * on;
       if constexpr (NORM) ss += q[k] * on;
     }
@@ -528,6 +433,22 @@ __device__ __forceinline__ void wg_reduce_unit(const GemmArgs& a, const WgArgs& 
   epi_store<EPI>(a, gt, m, lane, e, [&](int off) { return off ? pv : v; });
 }
 
+// The combine kernels' body: one wave per unit, a workgroup's 4 units on the XCD that wrote their column block's
+// slabs (wg_block_of).
+template <int BM, int EPI, bool NORM, int SLAB, int KS>
+__device__ __forceinline__ void wg_reduce_body(const GemmArgs& a, const WgArgs& w, int n_units) {
+  const int unit = wg_reduce_block(blockIdx.x, WG_NT * (BM / 16) / 4, w.xcd_blk) * 4 + (threadIdx.x >> 6);
+  if (unit >= n_units) return;
+  wg_reduce_unit<BM, EPI, NORM, SLAB, false>(a, w, unit, n_units, threadIdx.x & 63, KS ? KS : w.ks);
+}
+
+// Split-K combine + fused epilogue (wg_reduce_unit): one wave per 16 x 16 output unit; KS a
+// compile-time split count (0: the runtime-count fallback).
+template <int BM, int EPI, bool NORM, int KS, bool H16 = false>
+__global__ __launch_bounds__(256) void wgemm_reduce_kernel(const GemmArgs a, const WgArgs w, int n_units) {
+  wg_reduce_body<BM, EPI, NORM, wg_slab_mode(NORM, H16), KS>(a, w, n_units);
+}
+
 // In-launch split-K combine (the three wgemm_reduce_kernel launches per layer were 0.62 ms of the
 // 8.98 ms headline step).  The ks partners of a column block are one workgroup per CU, all resident together (the
 // host takes this path only when the grid fits the CU budget), so after publishing its slab write-through each
@@ -538,7 +459,7 @@ __device__ __forceinline__ void wg_reduce_unit(const GemmArgs& a, const WgArgs& 
 // claim bit decides who combines a piece, exactly once.  The workgroup that leaves the block last resets its three
 // words (arrivals, claims, exits) for the next launch.  Counters: w.counters[3 * blk + {0, 1, 2}], zero at rest.
 constexpr long long WG_INL_SPIN = 20000;  // s_memrealtime ticks (100 MHz): 200 us
-template <int BM, int EPI, bool NORM, bool H16>
+template <int BM, int EPI, bool NORM, int SLAB>
 __device__ void wg_inline_combine(const GemmArgs& a, const WgArgs& w, int blk, int kc, int n_units, int nthr,
                                   unsigned* flags) {
   unsigned& s_go = flags[0];
@@ -572,7 +493,8 @@ __device__ void wg_inline_combine(const GemmArgs& a, const WgArgs& w, int blk, i
   const int u0 = blk * upb;
   auto combine = [&](int piece) {  // units [piece * upb / ks, (piece + 1) * upb / ks) of the block
     const int b = piece * upb / ks, e = (piece + 1) * upb / ks;
-    for (int u = b + wave; u < e; u += nwaves) wg_reduce_unit<BM, EPI, NORM, H16, true>(a, w, u0 + u, n_units, lane, ks);
+    for (int u = b + wave; u < e; u += nwaves)
+      wg_reduce_unit<BM, EPI, NORM, SLAB, true>(a, w, u0 + u, n_units, lane, ks);
   };
   if (!s_claim) combine(kc);
   if (s_go == 2u) {
@@ -597,15 +519,10 @@ __device__ void wg_inline_combine(const GemmArgs& a, const WgArgs& w, int blk, i
 
 template <int BM, int EPI, bool NORM, bool H16 = false>
 void wg_reduce_launch(const GemmArgs& a, const WgArgs& w, int n_units, hipStream_t st) {
-  const dim3 grid((n_units + 3) / 4), blk(256);
-  switch (w.ks) {
-#define CAIN_WG_RED(K) \
-  case K: hipLaunchKernelGGL((wgemm_reduce_kernel<BM, EPI, NORM, K, H16>), grid, blk, 0, st, a, w, n_units); return;
-    CAIN_WG_RED(2) CAIN_WG_RED(3) CAIN_WG_RED(4) CAIN_WG_RED(5) CAIN_WG_RED(6) CAIN_WG_RED(7) CAIN_WG_RED(8)
-    CAIN_WG_RED(10) CAIN_WG_RED(12) CAIN_WG_RED(16)
-#undef CAIN_WG_RED
-    default: hipLaunchKernelGGL((wgemm_reduce_kernel<BM, EPI, NORM, 0, H16>), grid, blk, 0, st, a, w, n_units);
-  }
+  wg_with_ks(w.ks, std::integer_sequence<int, 2, 3, 4, 5, 6, 7, 8, 10, 12, 16>{}, [&](auto KS) {
+    hipLaunchKernelGGL((wgemm_reduce_kernel<BM, EPI, NORM, decltype(KS)::value, H16>), dim3((n_units + 3) / 4),
+                       dim3(256), 0, st, a, w, n_units);
+  });
 }
 
 namespace {
@@ -614,11 +531,9 @@ struct WgPlan {
   int bm, nblk, ks, kst;
   size_t part_floats, ss_floats, sc_floats;
   int variant = 0;  // ring variant (wg_launch_v)
-  int bnt = WG_NT;  // 16-column tiles per column block
 };
 
-// Split count: ~256 streaming workgroups (one per CU: the ring takes 128-144 KiB of LDS), at most 8 splits and
-// at least 4 stages per split.  Column-block counts >= 128 (gate/up, LM head) run unsplit.
+// Split targets of wg_split (<= 0: ~256 streaming workgroups, one per CU, and at most 8 splits).
 int g_wg_target = -1, g_wg_ksmax = -1;
 
 // Per-shape plan overrides (split count, ring variant) keyed by (N, K, row tile): set before any graph is captured
@@ -648,23 +563,19 @@ WgPlan wg_plan(int N, int K, int M) {
   const int target = g_wg_target > 0 ? g_wg_target : 256, ksmax = g_wg_ksmax > 0 ? g_wg_ksmax : 8;
   WgPlan p{};
   p.bm = M > 128 ? 256 : 128;
-  {
-    const WgShape* o = wg_shape(N, K, p.bm);
-    p.variant = o && o->variant >= 0 ? o->variant : g_wgemm_variant;
-  }
+  const WgShape* o = wg_shape(N, K, p.bm);
+  p.variant = o && o->variant >= 0 ? o->variant : g_wgemm_variant;
   p.nblk = ((N >> 4) + WG_NT - 1) / WG_NT;
   const int stages = K / WG_BK;
-  int ks = p.nblk >= 128 ? 1 : std::max(1, std::min(ksmax, (target + p.nblk / 2) / p.nblk));
+  // wg_split in its two steps, with the bf16-only rules between them
+  int want = wg_split_want(p.nblk, target, ksmax);
   // 256-row tiles with short splits (< 16 stages): ~3/4 of the workgroups, longer splits and fewer slabs.  In the
   // graph-replayed headline (llama3.1:8b, gpurun_out/r20-r21, same box, interleaved): O 8 -> 6 splits and QKV
   // 5 -> 4 took 26.5k -> 26.7k tok/s (each alone +1 %); down (28 stages per split at 8) lost at 6.
-  if (p.bm == 256 && ks > 1 && stages / ks < 16) ks = std::max(1, std::min(ks, (target * 3 / 4 + p.nblk / 2) / p.nblk));
-  if (const WgShape* o = wg_shape(N, K, p.bm)) {
-    if (o->ks > 0) ks = o->ks;
-  }
-  ks = std::min(ks, std::max(1, stages / 4));
-  p.kst = (stages + ks - 1) / ks;
-  p.ks = (stages + p.kst - 1) / p.kst;
+  if (p.bm == 256 && want > 1 && stages / want < 16) want = wg_split_want(p.nblk, target * 3 / 4, ksmax);
+  if (o && o->ks > 0) want = o->ks;
+  const WgSplit s = wg_split_even(stages, want);
+  p.ks = s.ks, p.kst = s.kst;
   if (p.ks > 1) {
     p.part_floats = (size_t)p.ks * p.nblk * WG_NT * (p.bm / 16) * 256;
     p.ss_floats = (size_t)p.nblk * p.ks * p.bm;
@@ -673,8 +584,8 @@ WgPlan wg_plan(int N, int K, int M) {
   return p;
 }
 
-// In-launch split-K combine (wg_inline_combine): cain_wgemm_set_inline(1) (CAIN_WGEMM_INLINE=1); 0 (default) the separate
-// wgemm_reduce_kernel launch (A/B, tests).  Taken only where every partner can be resident at once -- one
+// In-launch split-K combine (wg_inline_combine): cain_wgemm_set_inline(1) (CAIN_WGEMM_INLINE=1); 0, the default: the
+// separate wgemm_reduce_kernel launch.  Taken only where every partner can be resident at once -- one
 // workgroup per CU (the ring's LDS), so grid <= the CU budget -- and the block's words fit the counter region.
 int g_wg_inline = 0;
 inline bool wg_use_inline(const WgPlan& p) {
@@ -685,25 +596,15 @@ inline bool wg_use_inline(const WgPlan& p) {
 template <int BM, int DX, int DW, int EPI, bool NORM, int NDMA, int ABL = 0, bool H16 = true>
 hipError_t wg_launch(const GemmArgs& a, const WgArgs& w, const WgPlan& p, hipStream_t st) {
   using G = WgGeo<BM>;
-  constexpr int lds = (DW + 1) * G::W_BYTES + (DX + 1) * G::X_BYTES;
-  static_assert(lds <= 160 * 1024, "LDS");
-  auto set_lds = [](const void* k) {
-    return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
-  };
+  using Ring = RingLoader<BM, DX, DW, NDMA, 16, G::W_BYTES, 0, ABL != 2>;
+  const int grid = p.nblk * p.ks, threads = 64 * (8 + NDMA);
   if constexpr (ABL == 0) {
-    if (wg_use_inline(p)) {
-      static bool attr_inl = set_lds(reinterpret_cast<const void*>(&wgemm_kernel<BM, DX, DW, EPI, NORM, NDMA, 0, H16, true>));
-      if (!attr_inl) return hipErrorInvalidConfiguration;
-      hipLaunchKernelGGL((wgemm_kernel<BM, DX, DW, EPI, NORM, NDMA, 0, H16, true>), dim3(p.nblk * p.ks),
-                         dim3(64 * (8 + NDMA)), lds, st, a, w);
-      return hipGetLastError();
-    }
+    if (wg_use_inline(p))
+      return wg_launch_lds<&wgemm_kernel<BM, DX, DW, EPI, NORM, NDMA, 0, H16, true>, Ring::LDS_BYTES>(grid, threads,
+                                                                                                     st, a, w);
   }
-  static bool attr = set_lds(reinterpret_cast<const void*>(&wgemm_kernel<BM, DX, DW, EPI, NORM, NDMA, ABL, H16>));
-  if (!attr) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL((wgemm_kernel<BM, DX, DW, EPI, NORM, NDMA, ABL, H16>), dim3(p.nblk * p.ks), dim3(64 * (8 + NDMA)),
-                     lds, st, a, w);
-  hipError_t e = hipGetLastError();
+  const hipError_t e = wg_launch_lds<&wgemm_kernel<BM, DX, DW, EPI, NORM, NDMA, ABL, H16>, Ring::LDS_BYTES>(
+      grid, threads, st, a, w);
   if (e != hipSuccess || p.ks == 1) return e;
   wg_reduce_launch<BM, EPI, NORM, H16>(a, w, p.nblk * WG_NT * G::RB, st);
   return hipGetLastError();
@@ -735,15 +636,7 @@ hipError_t wg_launch_v(const GemmArgs& a, const WgArgs& w, const WgPlan& p, hipS
 
 template <int BM, bool NORM>
 hipError_t wg_launch_e(int epi, const GemmArgs& a, const WgArgs& w, const WgPlan& p, hipStream_t st) {
-  switch (epi) {
-    case EPI_BF16: return wg_launch_v<BM, EPI_BF16, NORM>(a, w, p, st);
-    case EPI_RESID: return wg_launch_v<BM, EPI_RESID, NORM>(a, w, p, st);
-    case EPI_F32: return wg_launch_v<BM, EPI_F32, NORM>(a, w, p, st);
-    case EPI_SILU: return wg_launch_v<BM, EPI_SILU, NORM>(a, w, p, st);
-    case EPI_GELU: return wg_launch_v<BM, EPI_GELU, NORM>(a, w, p, st);
-    case EPI_QKV_ROPE: return wg_launch_v<BM, EPI_QKV_ROPE, NORM>(a, w, p, st);
-    default: return hipErrorInvalidValue;
-  }
+  return wg_with_epi(epi, [&](auto E) { return wg_launch_v<BM, decltype(E)::value, NORM>(a, w, p, st); });
 }
 
 }  // namespace
@@ -754,7 +647,7 @@ CAIN_API int cain_wgemm_min_m() { return g_wgemm_min_m; }
 // A/B switches for tests and tuning tools (take effect for launches and graph captures after the call).
 CAIN_API void cain_wgemm_set_min_m(int m) { g_wgemm_min_m = m; }
 CAIN_API void cain_wgemm_set_variant(int v) { g_wgemm_variant = v; }
-// 0: separate reduce launch; 1: in-launch combine (default); 2: in-launch combine whose partners never wait, so the
+// 0 (default): separate reduce launch; 1: in-launch combine; 2: in-launch combine whose partners never wait, so the
 // last arriver combines every piece (the give-up path, for tests)
 CAIN_API void cain_wgemm_set_inline(int mode) { g_wg_inline = mode < 0 ? 0 : mode > 2 ? 2 : mode; }
 CAIN_API int cain_wgemm_get_inline() { return g_wg_inline; }
@@ -801,7 +694,6 @@ CAIN_API long long cain_wgemm_ws_bytes(int N, int K, int M) {
   return (long long)(WG_CTR_BYTES + (p.part_floats + p.ss_floats + p.sc_floats) * sizeof(float));
 }
 
-
 // a: the GEMM (gemm_epi.h); ws: >= cain_wgemm_ws_bytes of scratch (no zeroing needed).
 int wgemm_dispatch(const GemmArgs& a, int epi, bool norm, void* ws, long long ws_bytes, hipStream_t st) {
   if (!cain_wgemm_eligible(a.N, a.K, a.M)) return -1;
@@ -816,7 +708,6 @@ int wgemm_dispatch(const GemmArgs& a, int epi, bool norm, void* ws, long long ws
   // reduce 8.7 -> 6.9 us, QKV 22.5 + 11.2 -> 20.1 + 10.9 us, O / down main +1.1 us (their X panels are now
   // fetched per XCD); 25.8k -> 26.3k tok/s.
   w.xcd_blk = p.ks > 1 && p.nblk % 8 == 0;
-  w.bnt = p.bnt;
   // [counter region: 3 words per column block for the in-launch combine, zero at rest][slabs][sums]
   w.counters = static_cast<unsigned*>(ws);
   w.stamps = g_wg_stamps;

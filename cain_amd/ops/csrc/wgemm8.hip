@@ -8,8 +8,9 @@
 // (BASELINE.md); this is the MI355X 8-bit counterpart for the trial-batched decode step, reported
 // as its own configuration (bf16 stays the headline).
 //
-// Same LDS-DMA ring, loader waves, split-K slabs and epilogues as the bf16 kernel (wgemm.hip), and the SAME
-// LDS images: a ring stage is still one 128-B line per X row and 8 x 2 KiB of W, but it now spans 128 k, and
+// The LDS-DMA ring and its loader waves, the split-K slabs, the combine and the epilogues are the bf16 kernel's
+// (wgemm_ring.h: RingLoader, wg_store_slab16, wg_split, the launch helpers), and so are the LDS images: a
+// ring stage is still one 128-B line per X row and 8 x 2 KiB of W, but it now spans 128 k, and
 // its two 16-B fragment reads per operand (the bf16 kernel's two 32-k slices) are concatenated into the 32-B
 // operands of one block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 (unit e8m0 scales): per k twice the MFMA rate
 // of bf16 and half the bytes through HBM, the per-CU load path and LDS.  A and B only need the same k order in
@@ -22,10 +23,6 @@
 // scaled MFMA (cbsz 4: 16 B per lane), and the block scales ([N/16][K/128][64] e8m0 bytes, one per lane = one
 // 32-k block) go in as the MFMA's per-lane A scale.  A ring stage is 8 tiles x 1 KiB of W plus their 512 B of
 // scales; X (fp8 rows) is read as pieces 2g, 2g + 1 of its 128-B line, the lane's 32 k.  Y = xs[m] * sum.
-#include <algorithm>
-
-#include "common.h"
-#include "gemm_epi.h"
 #include "wgemm_ring.h"
 
 using namespace wg;
@@ -58,99 +55,33 @@ __device__ __forceinline__ f32x4 w8_scaled(f32x4 v, const W8Scales& q, int gt, i
   return v * w * x;
 }
 
-// W bytes of one ring stage: fp8 8 tiles x 2 KiB; fp4 8 tiles x 1 KiB + 8 x 64 B of scales
-template <int BM, bool FP4>
-constexpr int w8_wbytes() { return FP4 ? WG_NT * 1024 + WG_NT * 64 : WgGeo<BM>::W_BYTES; }
+// ring loader: fp8 16 W blocks per stage as bf16; fp4 8 blocks + 8 x 64 B of scales, as dword pieces
+template <int BM, int DX, int DW, int NDMA, bool FP4>
+using W8Ring = RingLoader<BM, DX, DW, NDMA, FP4 ? WG_NT : 16, FP4 ? WG_NT * 1024 + WG_NT * 64 : WgGeo<BM>::W_BYTES,
+                          FP4 ? 4 : 0>;
 
 template <int BM, int DX, int DW, int EPI, int NDMA, bool FP4 = false>
 __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm8_kernel(const GemmArgs a, const WgArgs w,
                                                                                   const W8Scales q) {
   using G = WgGeo<BM>;
-  constexpr int NX = DX + 1, NW = DW + 1;
-  constexpr int NLOAD = NDMA ? NDMA : 8;
-  constexpr int WPW = (FP4 ? WG_NT : 16) / NLOAD;  // W LDS-DMA pieces (1 KiB) per loader per stage
-  // fp4: the stage's 512 scale bytes as two 256-B dword pieces, issued by loaders 0 and 1 (spw of them per wave)
-  constexpr int XPW = (BM / 8) / NLOAD;
-  constexpr int WB = w8_wbytes<BM, FP4>();
-  static_assert(DW >= DX && DX >= 1, "W is issued no later than X of the same stage");
-  static_assert(WPW * NLOAD == (FP4 ? WG_NT : 16) && XPW * NLOAD == BM / 8, "loader split");
-  static_assert(!FP4 || NLOAD >= 2, "fp4 scale pieces: loaders 0 and 1");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const bool compute = wave < 8;
-  const bool loader = NDMA ? !compute : true;
-  const int lw = NDMA ? wave - 8 : wave;
   const int wm = wave % G::WM, wn = (wave / G::WM) % G::WN;
-  const int KH = a.K >> 6, ntiles = a.N >> 4;  // 1-KiB W blocks (16 rows x 64 k) per tile
+  const int ntiles = a.N >> 4;
   const int nblk = (ntiles + WG_NT - 1) / WG_NT;
 
   int blk, kc;
-  {
-    wg_block_of(blockIdx.x, w.ks, nblk, w.xcd_blk, blk, kc);
-  }
+  wg_block_of(blockIdx.x, w.ks, nblk, w.xcd_blk, blk, kc);
   const int tile0 = blk * WG_NT;
   const int st0 = kc * w.kst;
   const int nst = min(w.kst, (a.K >> 7) - st0);
-
-  const char* wsrc[WPW];
-#pragma unroll
-  for (int j = 0; j < WPW; ++j) {
-    if constexpr (FP4) {  // tile tn's 1-KiB block of 128 k per stage
-      const int tn = lw * WPW + j;
-      wsrc[j] = reinterpret_cast<const char*>(a.Wp) +
-                ((size_t)min(tile0 + tn, ntiles - 1) * (KH >> 1) + (size_t)st0) * 1024 + lane * 16;
-    } else {
-      const int qq = lw * WPW + j, tn = qq >> 1, h = qq & 1;
-      wsrc[j] = reinterpret_cast<const char*>(a.Wp) +
-                ((size_t)min(tile0 + tn, ntiles - 1) * KH + (size_t)st0 * 2 + h) * 1024 + lane * 16;
-    }
-  }
-  // fp4 scales: loader lw < 2 copies the 64 scale bytes of tiles 4 lw .. 4 lw + 3 (lane: tile 4 lw + lane / 16,
-  // dword lane % 16)
-  const char* ssrc = nullptr;
-  const int spw = FP4 && loader && lw < 2 ? 1 : 0;
-  if constexpr (FP4) {
-    const int tn = 4 * max(min(lw, 1), 0) + (lane >> 4);
-    ssrc = reinterpret_cast<const char*>(q.ws) + ((size_t)min(tile0 + tn, ntiles - 1) * (KH >> 1) + (size_t)st0) * 64 +
-           (lane & 15) * 4;
-  }
-  const char* xsrc[XPW];
-#pragma unroll
-  for (int j = 0; j < XPW; ++j) {
-    const int i = lw + NLOAD * j;
-    const int r = 8 * i + (lane >> 3);
-    const int p = (lane & 7) ^ ((r >> 1) & 7);
-    xsrc[j] = reinterpret_cast<const char*>(a.X) + (size_t)min(r, a.M - 1) * a.ldx + (size_t)st0 * W8_BK + p * 16;
-  }
-  char* const xring = smem + NW * WB;
-  auto issue_w = [&](int t) {
-    char* base = smem + (t % NW) * WB;
-#pragma unroll
-    for (int j = 0; j < WPW; ++j) glds16(wsrc[j] + (size_t)t * (FP4 ? 1024 : 2048), base + (lw * WPW + j) * 1024, 1);
-    if constexpr (FP4) {
-      if (spw)
-        __builtin_amdgcn_global_load_lds((gbl_void_t*)(ssrc + (size_t)t * 64),
-                                         (lds_void_t*)(base + WG_NT * 1024 + lw * 256), 4, 0, 0);
-    }
-  };
-  auto issue_x = [&](int t) {
-    char* base = xring + (t % NX) * G::X_BYTES;
-#pragma unroll
-    for (int j = 0; j < XPW; ++j) glds16(xsrc[j] + (size_t)t * W8_BK, base + (lw + NLOAD * j) * 1024, 0);
-  };
-  auto younger_than = [&](int t) {
-    int n = 0;
-#pragma unroll
-    for (int u = t - DX + 1; u < t; ++u) n += (WPW + spw) * (u + DW < nst) + XPW * (u + DX < nst);
-    return n;
-  };
-  auto issue_step = [&](int t) {
-    if (loader) {
-      if (t + DW < nst) issue_w(t + DW);
-      if (t + DX < nst) issue_x(t + DX);
-    }
-  };
+  // W per tile: fp8 K / 64 blocks of 1 KiB (16 rows x 64 k), two per stage; fp4 K / 128 blocks (16 rows x 128 k)
+  // and as many 64-B scale groups, one per stage.  X: e4m3 rows of ldx bytes.
+  const W8Ring<BM, DX, DW, NDMA, FP4> ring(smem, wave, lane, a.Wp, FP4 ? a.K >> 7 : a.K >> 6, FP4 ? st0 : st0 * 2,
+                                          reinterpret_cast<const char*>(a.X) + (size_t)st0 * W8_BK, a.ldx, a.M,
+                                          ntiles, tile0, nst, q.ws);
 
   const int c = lane & 15, g = lane >> 4;
   int woff[G::TN];
@@ -170,29 +101,18 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm8_kernel
 #pragma unroll
     for (int mb = 0; mb < G::MB; ++mb) acc[tn][mb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  if (loader) {
-#pragma unroll
-    for (int u = -DW; u < 0; ++u) {
-      if (u + DW < nst) issue_w(u + DW);
-      if (u + DX >= 0 && u + DX < nst) issue_x(u + DX);
-    }
-  }
-
   // one barrier per stage for every wave; after barrier t the loaders refill stage t - 1's slots (every wave's
   // reads of stage t - 1 completed before it: lgkmcnt(0) in ring_barrier)
   if (NDMA && !compute) {  // loader waves: their own loop, so the two roles' registers never overlap
-    for (int t = 0; t < nst; ++t) {
-      wait_vmcnt_rt(younger_than(t));
-      ring_barrier();
-      issue_step(t);
-    }
+    ring.loader_loop();
   } else {
+    if constexpr (!NDMA) ring.prologue();
     for (int t = 0; t < nst; ++t) {
-      if constexpr (!NDMA) wait_vmcnt_rt(younger_than(t));
+      if constexpr (!NDMA) ring.land(t);
       ring_barrier();
-      if constexpr (!NDMA) issue_step(t);
-      const char* wbase = smem + (t % NW) * WB;
-      const char* xbase = xring + (t % NX) * G::X_BYTES + xrow0;
+      if constexpr (!NDMA) ring.issue_step(t);
+      const char* wbase = ring.w_slot(t);
+      const char* xbase = ring.x_slot(t) + xrow0;
       i32x4 b0[G::MB], b1[G::MB], a0[G::TN], a1[G::TN];
       int sa[G::TN];
 #pragma unroll
@@ -229,9 +149,10 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm8_kernel
   ring_barrier();
   if (!compute) return;
 
+  // every output gets its row scales (w8_scaled); tiles past N keep their (unused) sums
   if (w.ks > 1) {
-    // slabs in fp16 as the bf16 kernel's (wgemm.hip OPT 32), already scaled (the scales are linear, so the reduce
-    // sums scaled partials): the raw e4m3 x e4m3 sums would overflow fp16
+    // slabs in fp16 as the bf16 kernel's, already scaled (the scales are linear, so the reduce sums scaled
+    // partials): the raw e4m3 x e4m3 sums would overflow fp16
     const int n_units = nblk * WG_NT * G::RB;
 #pragma unroll
     for (int tn = 0; tn < G::TN; ++tn)
@@ -240,11 +161,9 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm8_kernel
         const int gt = tile0 + wn * G::TN + tn;
         const int unit = gt * G::RB + wm * G::MB + mb;
         const int m = (wm * G::MB + mb) * 16 + c;
-        const f32x4 v = gt < ntiles ? w8_scaled<FP4>(acc[tn][mb], q, gt, m, lane, a.M) : acc[tn][mb];
-        f16x4 h;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) h[i] = (_Float16)fminf(fmaxf(v[i], -65504.f), 65504.f);
-        reinterpret_cast<f16x4*>(w.part)[((size_t)kc * n_units + unit) * 64 + lane] = h;
+        wg_store_slab16(w.part, wg_slab_at(kc, n_units, unit, lane), acc[tn][mb], [&](const f32x4& v) {
+          return gt < ntiles ? w8_scaled<FP4>(v, q, gt, m, lane, a.M) : v;
+        });
       }
     return;
   }
@@ -267,8 +186,9 @@ __global__ __launch_bounds__(64 * (8 + NDMA), (8 + NDMA) / 4) void wgemm8_kernel
 }
 
 // Split-K combine + fused epilogue: one wave per 16 x 16 output unit (the slabs hold scaled fp16 partials).  As
-// wgemm.hip's reduce: the epilogue inputs and all KS slab pieces are issued before the first add (KS = 0: runtime
-// count).
+// wg_reduce_unit, the epilogue inputs and all KS slab pieces are issued before the first add (KS = 0: runtime
+// count); kept apart from it because the QKV epilogue's rounding follows how the compiler fuses its multiply-adds
+// with the sum before them (profiles/r10/wide_ring_share/README.md).
 template <int BM, int EPI, int KS>
 __global__ __launch_bounds__(256) void wgemm8_reduce_kernel(const GemmArgs a, const WgArgs w, const W8Scales q,
                                                             int n_units) {
@@ -366,11 +286,8 @@ W8Plan w8_plan(int N, int K, int M) {
   W8Plan p{};
   p.bm = M > 128 ? 256 : 128;
   p.nblk = ((N >> 4) + WG_NT - 1) / WG_NT;
-  const int stages = K / W8_BK;
-  int ks = p.nblk >= 128 ? 1 : std::max(1, std::min(8, (256 + p.nblk / 2) / p.nblk));
-  ks = std::min(ks, std::max(1, stages / 4));
-  p.kst = (stages + ks - 1) / ks;
-  p.ks = (stages + p.kst - 1) / p.kst;
+  const WgSplit s = wg_split(p.nblk, K / W8_BK, 256, 8);
+  p.ks = s.ks, p.kst = s.kst;
   if (p.ks > 1) p.part_floats = (size_t)p.ks * p.nblk * WG_NT * (p.bm / 16) * 256;
   return p;
 }
@@ -378,26 +295,15 @@ W8Plan w8_plan(int N, int K, int M) {
 template <int BM, int DX, int DW, int EPI, int NDMA, bool FP4 = false>
 hipError_t w8_launch(const GemmArgs& a, const WgArgs& w, const W8Scales& q, const W8Plan& p, hipStream_t st) {
   using G = WgGeo<BM>;
-  constexpr int lds = (DW + 1) * w8_wbytes<BM, FP4>() + (DX + 1) * G::X_BYTES;
-  static_assert(lds <= 160 * 1024, "LDS");
-  static bool attr = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&wgemm8_kernel<BM, DX, DW, EPI, NDMA, FP4>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess;
-  }();
-  if (!attr) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL((wgemm8_kernel<BM, DX, DW, EPI, NDMA, FP4>), dim3(p.nblk * p.ks), dim3(64 * (8 + NDMA)), lds, st,
-                     a, w, q);
-  hipError_t e = hipGetLastError();
+  constexpr int lds = W8Ring<BM, DX, DW, NDMA, FP4>::LDS_BYTES;
+  const hipError_t e =
+      wg_launch_lds<&wgemm8_kernel<BM, DX, DW, EPI, NDMA, FP4>, lds>(p.nblk * p.ks, 64 * (8 + NDMA), st, a, w, q);
   if (e != hipSuccess || p.ks == 1) return e;
   const int n_units = p.nblk * WG_NT * G::RB;
-  const dim3 grid((n_units + 3) / 4), blk(256);
-  switch (w.ks) {
-#define CAIN_W8_RED(K) \
-  case K: hipLaunchKernelGGL((wgemm8_reduce_kernel<BM, EPI, K>), grid, blk, 0, st, a, w, q, n_units); break;
-    CAIN_W8_RED(2) CAIN_W8_RED(3) CAIN_W8_RED(4) CAIN_W8_RED(5) CAIN_W8_RED(6) CAIN_W8_RED(7) CAIN_W8_RED(8)
-#undef CAIN_W8_RED
-    default: hipLaunchKernelGGL((wgemm8_reduce_kernel<BM, EPI, 0>), grid, blk, 0, st, a, w, q, n_units);
-  }
+  wg_with_ks(w.ks, std::integer_sequence<int, 2, 3, 4, 5, 6, 7, 8>{}, [&](auto KS) {
+    hipLaunchKernelGGL((wgemm8_reduce_kernel<BM, EPI, decltype(KS)::value>), dim3((n_units + 3) / 4), dim3(256), 0, st,
+                       a, w, q, n_units);
+  });
   return hipGetLastError();
 }
 
@@ -406,15 +312,7 @@ hipError_t w8_launch_e(int epi, const GemmArgs& a, const WgArgs& w, const W8Scal
                        hipStream_t st) {
   // 160 KiB rings, as the bf16 defaults; fp4's 8.5-KiB W stages: the same X ring, 6 W stages (147 / 115 KiB)
   constexpr int DX = BM == 256 ? 2 : 3, DW = FP4 ? 5 : (BM == 256 ? 3 : 5);
-  switch (epi) {
-    case EPI_BF16: return w8_launch<BM, DX, DW, EPI_BF16, 4, FP4>(a, w, q, p, st);
-    case EPI_RESID: return w8_launch<BM, DX, DW, EPI_RESID, 4, FP4>(a, w, q, p, st);
-    case EPI_F32: return w8_launch<BM, DX, DW, EPI_F32, 4, FP4>(a, w, q, p, st);
-    case EPI_SILU: return w8_launch<BM, DX, DW, EPI_SILU, 4, FP4>(a, w, q, p, st);
-    case EPI_GELU: return w8_launch<BM, DX, DW, EPI_GELU, 4, FP4>(a, w, q, p, st);
-    case EPI_QKV_ROPE: return w8_launch<BM, DX, DW, EPI_QKV_ROPE, 4, FP4>(a, w, q, p, st);
-    default: return hipErrorInvalidValue;
-  }
+  return wg_with_epi(epi, [&](auto E) { return w8_launch<BM, DX, DW, decltype(E)::value, 4, FP4>(a, w, q, p, st); });
 }
 
 }  // namespace

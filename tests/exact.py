@@ -330,15 +330,15 @@ def product(x: torch.Tensor, ew: Weights) -> torch.Tensor:
 
 
 def wide_k_ranges(K: int, ks: int, stage: int = 64) -> List[Tuple[int, int]]:
-    """The k ranges of a wide-GEMM launch with ``ks`` splits (wgemm.hip wg_plan / wgemm8.hip w8_plan: stages of 64 /
-    128 k, kst = ceil(stages / ks) stages per range)."""
+    """The k ranges of a wide-GEMM launch with ``ks`` splits (wgemm_ring.h wg_split_even, for wgemm.hip wg_plan /
+    wgemm8.hip w8_plan: stages of 64 / 128 k, kst = ceil(stages / ks) stages per range)."""
     stages = K // stage
     kst = -(-stages // ks)
     return [(i * kst * stage, min((i + 1) * kst * stage, K)) for i in range(-(-stages // kst))]
 
 
 def a8_splits(N: int, K: int) -> int:
-    """Split count of the W8A8 / W4A8 wide kernels (the mirror of wgemm8.hip w8_plan)."""
+    """Split count of the W8A8 / W4A8 wide kernels (the mirror of wgemm8.hip w8_plan = wgemm_ring.h wg_split)."""
     nblk = (N // 16 + 7) // 8
     stages = K // 128
     ks = 1 if nblk >= 128 else max(1, min(8, (256 + nblk // 2) // nblk))

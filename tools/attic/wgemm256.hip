@@ -1,4 +1,5 @@
 // Wide-batch projection GEMM with 256-column workgroup tiles (BM = 256 rows x BN = 256 columns), gfx950.
+// (Not built.  Last matched csrc/wgemm_ring.h at commit f3a3b6e: it needs WgArgs::bnt and WgGeo::XPW, since removed.)
 //
 //   Y[m][n] = epilogue( inv[m] * sum_k X[m][k] * W[n][k] )        (M in (128, 256]: the trial-batched decode step)
 //

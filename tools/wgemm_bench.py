@@ -6,7 +6,10 @@ Weights rotate over enough copies that every call streams from HBM (> 2x the 256
 a real decode step where each layer's weights are read once.  Prints one JSON line per (shape, M, path):
 us per call and effective weight TB/s; plus the numerics of the wide kernel vs an fp32 reference.
 
-    python tools/wgemm_bench.py [--model llama3.1:8b] [--rows 128,256] [--iters 20]
+    python tools/wgemm_bench.py [--model llama3.1:8b] [--rows 128,256] [--iters 20] [--weights bf16,fp8,fp4]
+
+--weights fp8 / fp4 time the W8A8 / W4A8 wide kernels (csrc/wgemm8.hip: cain_gemm_w8a8 / cain_gemm_w4a8 on rows
+quantised once, outside the timed loop) the same way: one JSON line per (shape, M) with "weights" and "wide_us".
 """
 from __future__ import annotations
 
@@ -21,7 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from cain_amd import ops  # noqa: E402
 from cain_amd.models.config import get_config  # noqa: E402
-from cain_amd.models.weights import pack_mfma_a  # noqa: E402
+from cain_amd.models.weights import (pack_mfma_a, pack_mfma_a_fp8_k128, pack_mxfp4, quantize_fp8_rows,  # noqa: E402
+                                     quantize_mxfp4)
 
 
 def shapes(cfg):
@@ -30,6 +34,50 @@ def shapes(cfg):
             ("gateup", 2 * cfg.ffn, cfg.d_model, ops.EPI_SILU, True),
             ("down", cfg.d_model, cfg.ffn, ops.EPI_RESID, False),
             ("lm_head", cfg.vocab, cfg.d_model, ops.EPI_F32, True)]
+
+
+def time_a8(ns, lib, fmt, name, N, K, epi, norm, rows, dev):
+    """The fp8 / fp4 wide kernels on the rotating weight copies (the launch alone: x8 / xs are quantised before)."""
+    wbytes = N * K if fmt == "fp8" else N * K // 2 + N * K // 32
+    ncopy = max(2, -(-(512 << 20) // wbytes))
+    torch.manual_seed(0)
+    W = (torch.randn(N, K, device=dev) * 0.02).bfloat16()
+    if fmt == "fp8":
+        q, s = quantize_fp8_rows(W)
+        one = (pack_mfma_a_fp8_k128(q), s.contiguous())
+    else:
+        one = pack_mxfp4(*quantize_mxfp4(W))
+    packs = [one] + [tuple(t.clone() for t in one) for _ in range(ncopy - 1)]
+    fn = lib.cain_gemm_w8a8 if fmt == "fp8" else lib.cain_gemm_w4a8
+    for M in rows:
+        x = (2 * torch.randn(M, K, device=dev)).bfloat16()
+        x8, xs = ops.quant_rows(x, norm, 1e-6)
+        n_out = N // 2 if epi in (ops.EPI_SILU, ops.EPI_GELU) else N
+        out = torch.zeros(M, n_out, device=dev, dtype=torch.float32 if epi == ops.EPI_F32 else torch.bfloat16)
+        nbytes = int(lib.cain_w8a8_ws_bytes(N, K, M))
+        ws = torch.zeros(max(nbytes, 16), device=dev, dtype=torch.uint8)
+        st = ops._stream()
+
+        def run(i):
+            wq, sc = packs[i % ncopy]
+            rc = fn(ops._p(wq), ops._p(sc), ops._p(x8), K, ops._p(xs), K, N, M, ops._p(out), out.stride(0), None, None,
+                    None, None, None, None, None, 0, 0, 0, 0, ops._p(ws), nbytes, epi, st)
+            assert rc == 0, rc
+
+        for i in range(3):
+            run(i)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for i in range(ns.iters):
+            run(i)
+        b.record()
+        torch.cuda.synchronize()
+        us = a.elapsed_time(b) * 1000.0 / ns.iters
+        print(json.dumps({"model": ns.model, "weights": fmt, "shape": name, "N": N, "K": K, "M": M,
+                          "wide_us": round(us, 2), "wide_TBps": round(wbytes / (us * 1e-6) / 1e12, 3)}), flush=True)
+    del packs
+    torch.cuda.empty_cache()
 
 
 def main() -> int:
@@ -42,6 +90,7 @@ def main() -> int:
     ap.add_argument("--no-old", action="store_true")
     ap.add_argument("--variants", default="0", help="ring variants to time (csrc/wgemm.hip wg_launch_v)")
     ap.add_argument("--splits", default="", help="split plans target:ksmax,... to time (default plan only)")
+    ap.add_argument("--weights", default="bf16", help="weight formats to time: bf16, fp8 (W8A8), fp4 (W4A8)")
     ns = ap.parse_args()
     cfg = get_config(ns.model)
     dev = torch.device("cuda")
@@ -55,6 +104,10 @@ def main() -> int:
     rows = [int(r) for r in ns.rows.split(",")]
     for name, N, K, epi, norm in shapes(cfg):
         if ns.only and name not in ns.only.split(","):
+            continue
+        for fmt in [f for f in ns.weights.split(",") if f in ("fp8", "fp4")]:
+            time_a8(ns, lib, fmt, name, N, K, epi, norm, rows, dev)
+        if "bf16" not in ns.weights.split(","):
             continue
         wbytes = N * K * 2
         ncopy = max(2, -(-(512 << 20) // wbytes))
@@ -81,7 +134,7 @@ def main() -> int:
                 torch.cuda.synchronize()
                 return a.elapsed_time(b) * 1000.0 / ns.iters
 
-            res = {"model": ns.model, "shape": name, "N": N, "K": K, "M": M}
+            res = {"model": ns.model, "weights": "bf16", "shape": name, "N": N, "K": K, "M": M}
             # numerics of the wide path (F32 epilogue, one copy)
             lib.cain_wgemm_set_min_m(64)
             y = ops.skinny_gemm(Wp[0], x, N, ops.EPI_F32, norm=norm, eps=1e-6)
