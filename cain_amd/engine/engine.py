@@ -40,6 +40,8 @@ import torch
 from ..models.config import ModelConfig, get_config, rope_inv_freq
 from ..models.hf import checkpoint_for, load_hf_weights, load_pretrained, load_tokenizer
 from ..models.tokenizer import get_tokenizer
+from .speculative import K_MAX, SeqState
+from .speculative import draft as spec_draft_host
 from ..models.weights import WEIGHT_DTYPES, ModelWeights, pack_for_engine, random_weights, roundtrip_weights
 
 #: Ollama's default sampling options (SURVEY §2.4 "Sampling" row)
@@ -75,6 +77,12 @@ class GenResult:
     # distribution, logit descending, index ascending on ties
     logprobs: Optional[List[float]] = None
     top_logprobs: Optional[List[List[tuple]]] = None
+    # speculative decoding (None: the mode is off): drafts proposed, generated tokens that were accepted drafts, the
+    # decode steps the row was live for, and the tokens each of those steps committed
+    draft_count: Optional[int] = None
+    draft_accepted: Optional[int] = None
+    decode_steps: Optional[int] = None
+    step_tokens: Optional[List[int]] = None
 
     @property
     def prompt_eval_count(self) -> int:
@@ -105,6 +113,9 @@ class GenResult:
         }
         if self.prompt_cached > 0:
             d["prompt_cached_count"] = int(self.prompt_cached)
+        if self.draft_count is not None:
+            d["draft_count"] = int(self.draft_count)
+            d["draft_accepted_count"] = int(self.draft_accepted or 0)
         return d
 
 
@@ -356,7 +367,7 @@ class DecodeEngine:
                  max_batch: int = 16, max_context: int = 2048, seed: int = 0, backend: Optional[str] = None,
                  steps_per_graph: int = 8, weights: Optional[ModelWeights] = None, tokenizer=None,
                  keep_natural: bool = False, weight_dtype: str = "bf16", kv_dtype: str = "bf16", cu_limit: int = 0,
-                 prefix_cache: Optional[bool] = None):
+                 prefix_cache: Optional[bool] = None, speculative: Optional[int] = None):
         """``weight_dtype="fp8"``: GEMM weights quantised per row to e4m3 (half the weight bytes per decode step):
         forwards of up to 16 rows run W8A16 (gemm_w8.hip, bf16 activations), wider ones W8A8 (wgemm8.hip: the
         activations quantised per row to e4m3, fp8 MFMA) up to 256 rows; CAIN_W8A8=0 keeps W8A16 only (<= 64
@@ -384,7 +395,13 @@ class DecodeEngine:
         (``slot_tokens``) and a new request prefills only what differs from the best matching slot
         (``plan_prefix_reuse``; a prefix held by a slot that is still decoding is copied, csrc/kv_prefix.hip).  Off
         by default (None: ``CAIN_PREFIX_CACHE=1`` turns it on): without it every admit prefills from position 0 and
-        the caches hold exactly what the requests wrote."""
+        the caches hold exactly what the requests wrote.
+        ``speculative``: K in 0 .. 7 drafts per sequence and decode step (engine/speculative.py: n-gram lookup in the
+        request's own tokens, or drafts given to ``generate``), verified K + 1 rows per sequence in one forward; a
+        draft is kept only when it is the token the sampler draws, so drafts change the number of steps, not the
+        tokens (a K + 1-row forward rounds differently from a 1-row one: against a plain engine, equal up to near-ties).  0 (default; None: ``CAIN_SPECULATIVE``): off, nothing changes.  A
+        batch then holds at most ``rows per forward // (K + 1)`` sequences; not together with ``prefix_cache`` or
+        ``logprobs``."""
         self.cfg = get_config(model) if isinstance(model, str) else model
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
@@ -400,6 +417,13 @@ class DecodeEngine:
         self.cu_limit = int(cu_limit)
         self.prefix_cache = (os.environ.get("CAIN_PREFIX_CACHE", "0") == "1") if prefix_cache is None \
             else bool(prefix_cache)
+        self.speculative = int(os.environ.get("CAIN_SPECULATIVE", "0") or 0) if speculative is None \
+            else int(speculative)
+        if not 0 <= self.speculative <= K_MAX:
+            raise ValueError(f"speculative must be in 0..{K_MAX}, got {self.speculative}")
+        if self.speculative and self.prefix_cache:
+            raise ValueError("speculative decoding and prefix_cache cannot be combined (the slot records assume one "
+                             "token per step)")
         self.prefill_rows_total = 0  # rows fed to prefill forwards so far
         if self.cu_limit and (self.cu_limit < 0 or self.cu_limit % 8):
             raise ValueError(f"cu_limit must be a positive multiple of 8 (or 0), got {cu_limit}")
@@ -415,7 +439,9 @@ class DecodeEngine:
         if backend is None:
             backend = "hip" if self.device.type == "cuda" else "torch"
         self.backend = backend
-        self.max_batch = int(min(max_batch, row_cap))
+        self.row_cap = int(row_cap)
+        # speculative: a forward verifies K + 1 rows per sequence, so fewer sequences fit the rows of one forward
+        self.max_batch = int(max(1, min(max_batch, row_cap // (self.speculative + 1))))
         # prompt tokens per prefill forward: the engine's own row count when that is wider (a 256-row engine
         # prefills 256 tokens per forward on the wide GEMM: half the launches of 128-row chunks)
         self.prefill_chunk = int(min(int(os.environ.get("CAIN_PREFILL_ROWS", "0") or 0)
@@ -475,7 +501,8 @@ class DecodeEngine:
         ang = np.arange(T, dtype=np.float64)[:, None] * inv[None, :]
         self.cos_t = torch.tensor(np.cos(ang), dtype=torch.float32, device=dev).contiguous()
         self.sin_t = torch.tensor(np.sin(ang), dtype=torch.float32, device=dev).contiguous()
-        R = max(self.max_batch, self.prefill_chunk)  # rows any forward of this engine can have
+        # rows any forward of this engine can have (speculative: K + 1 rows per sequence)
+        R = max(self.max_batch * (self.speculative + 1), self.prefill_chunk)
         z = lambda *s, dt=bf: torch.zeros(*s, device=dev, dtype=dt)  # noqa: E731
         self.buf = dict(x=z(R, cfg.d_model), q=z(R, cfg.q_dim), attn=z(R, cfg.q_dim), act=z(R, cfg.ffn),
                         logits=z(R, cfg.vocab, dt=torch.float32), counters=z(R * cfg.n_kv_heads, dt=torch.int32))
@@ -538,6 +565,7 @@ class DecodeEngine:
         d.flm_head = MFMT[packed["flm_head"]] if "flm_head" in packed else 0
         self._desc = d
         self._lp: Optional[Dict[str, torch.Tensor]] = None  # logprob buffers, allocated at first use (_lp_bufs)
+        self._spec: Optional[Dict] = None  # speculative buffers, allocated at first use (_spec_bufs)
         self._plans: Dict[int, int] = {}
         self._graphs: Dict[tuple, int] = {}
         self._cu_stream = None
@@ -681,6 +709,81 @@ class DecodeEngine:
             self._graphs[key] = g
         return g
 
+    # ---------------------------------------------------------------- speculative decoding
+    def _spec_bufs(self) -> Dict:
+        """Device buffers of speculative decoding (csrc/spec.h), made when the mode first runs."""
+        if self._spec is None:
+            from .. import ops
+
+            self._spec = ops.spec_alloc(self.max_batch, self.speculative, self.max_batch, self.T_max, self.cfg.vocab,
+                                        self.device)
+        return self._spec
+
+    def _spec_begin(self, rows: Sequence[int], slots: Sequence[int], ids, drafts=None) -> None:
+        """Decode rows ``rows`` start requests ``ids`` in cache slots ``slots``: their records hold the prompts, their
+        counters start at zero, their given drafts (``drafts[i]``: ids by generated index, or None) are stored."""
+        b = self._spec_bufs()
+        rec = torch.zeros(len(ids), self.T_max, dtype=torch.int32)
+        giv = torch.full((len(ids), self.T_max), -1, dtype=torch.int32)
+        for i, p in enumerate(ids):
+            rec[i, :len(p)] = torch.tensor(p, dtype=torch.int32)
+            if drafts is not None and drafts[i] is not None:
+                g = [int(t) for t in drafts[i]][: self.T_max]
+                if any(t >= self.cfg.vocab for t in g):
+                    raise ValueError(f"draft id outside the vocabulary ({self.cfg.vocab})")
+                giv[i, :len(g)] = torch.tensor(g, dtype=torch.int32)
+        ri = torch.tensor(list(rows), dtype=torch.long, device=self.device)
+        b["seq"][torch.tensor(list(slots), dtype=torch.long, device=self.device)] = rec.to(self.device)
+        b["given"][ri] = giv.to(self.device)
+        for k in ("drafted", "accepted", "n_step"):
+            b[k][ri] = 0
+
+    def _spec_stats(self, row: int) -> Dict:
+        """Counters of decode row ``row``: drafts proposed, drafts accepted, live steps, tokens per step."""
+        b = self._spec_bufs()
+        n = int(b["n_step"][row])
+        return dict(draft_count=int(b["drafted"][row]), draft_accepted=int(b["accepted"][row]), decode_steps=n,
+                    step_tokens=b["step_tokens"][row, :min(n, self.T_max)].cpu().tolist())
+
+    def _forward_spec(self, B: int, mode: int) -> None:
+        from .. import ops
+
+        lib = ops.load_spec()
+        rs, sp = self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), mode)
+        plan = self._plan(B * (self.speculative + 1))
+        _set_cu_budget(self.lib, self.cu_limit)
+        try:
+            rc = lib.cain_plan_forward_spec(ctypes.c_void_p(plan), B, ctypes.byref(rs), ctypes.byref(sp),
+                                            ctypes.c_void_p(self.stream.cuda_stream))
+        finally:
+            _set_cu_budget(self.lib, 0)
+        if rc != 0:
+            where = self.lib.cain_plan_last_failure()
+            raise RuntimeError(f"cain_plan_forward_spec failed rc={rc}" + (f" at {where.decode()}" if where else ""))
+
+    def _graph_spec(self, B: int, steps: int, mode: int) -> int:
+        """``steps`` speculative steps (draft -> verify forward over ``B (K + 1)`` rows -> accept) over ``B``
+        sequences as one graph; cache entries of their own, beside the plain graphs."""
+        from .. import ops
+
+        key = (B, steps, "spec", mode)
+        g = self._graphs.get(key)
+        if g is None:
+            lib = ops.load_spec()
+            rs, sp = self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), mode)
+            err = ctypes.c_int(0)
+            plan = self._plan(B * (self.speculative + 1))
+            _set_cu_budget(self.lib, self.cu_limit)
+            try:
+                g = lib.cain_plan_capture_spec(ctypes.c_void_p(plan), B, ctypes.byref(rs), ctypes.byref(sp), steps,
+                                               ctypes.c_void_p(self.stream.cuda_stream), ctypes.byref(err))
+            finally:
+                _set_cu_budget(self.lib, 0)
+            if not g:
+                raise RuntimeError(f"hipGraph capture of the speculative steps failed (err={err.value})")
+            self._graphs[key] = g
+        return g
+
     def close(self) -> None:
         lib = getattr(self, "lib", None)
         if lib is None:
@@ -711,7 +814,8 @@ class DecodeEngine:
                  options: Union[None, Dict, Sequence[Optional[Dict]]] = None, use_graph: bool = True,
                  on_tokens=None, context: Optional[Sequence[Optional[Sequence[int]]]] = None,
                  logprobs: Union[bool, Sequence[bool]] = False,
-                 top_logprobs: Union[int, Sequence[int]] = 0) -> List[GenResult]:
+                 top_logprobs: Union[int, Sequence[int]] = 0,
+                 drafts: Optional[Sequence[Optional[Sequence[int]]]] = None) -> List[GenResult]:
         """Generate for a batch of prompts (ids or text).  ``on_tokens(list_per_row)`` streams newly
         generated ids every ``steps_per_graph`` decode steps (and stops early once every row is done).
         ``context[i]``: token ids prepended to row i's encoded prompt (Ollama's ``context`` of an earlier answer).
@@ -720,12 +824,20 @@ class DecodeEngine:
         top-p -- and the ``top_logprobs`` (0 .. 20) most likely ``(id, logprob)`` of that distribution per token,
         logit descending, index ascending on ties.  On the HIP backend both are computed on the device inside the
         decode graphs (csrc/logprob.hip); the tokens are the same with and without.  With logprobs asked for,
-        ``on_tokens`` gets a second argument: per row ``(logprobs, top_logprobs)`` of the new tokens, or None."""
+        ``on_tokens`` gets a second argument: per row ``(logprobs, top_logprobs)`` of the new tokens, or None.
+        ``drafts`` (speculative engines): per row the draft token of every generated index (a negative id ends a
+        step's draft; None: no drafts for that row); this call then verifies these instead of the n-gram lookup's."""
         prompts = list(prompts)
         B = len(prompts)
         if B == 0:
             return []
         want = _want_logprobs(logprobs, top_logprobs, B)
+        if self.speculative and any(w >= 0 for w in want):
+            raise ValueError("logprobs cannot be combined with speculative decoding")
+        if drafts is not None and not self.speculative:
+            raise ValueError("drafts need an engine with speculative > 0")
+        if drafts is not None and len(drafts) != B:
+            raise ValueError(f"{len(drafts)} drafts for {B} prompts")
         if B > self.max_batch:
             out = []
             for i in range(0, B, self.max_batch):
@@ -734,7 +846,8 @@ class DecodeEngine:
                 ops_ = options[sl] if isinstance(options, (list, tuple)) else options
                 out += self.generate(prompts[sl], nps, ops_, use_graph, on_tokens,
                                      context[sl] if context is not None else None,
-                                     [w >= 0 for w in want[sl]], [max(w, 0) for w in want[sl]])
+                                     [w >= 0 for w in want[sl]], [max(w, 0) for w in want[sl]],
+                                     drafts[sl] if drafts is not None else None)
             return out
         if context is not None and len(context) != B:
             raise ValueError(f"{len(context)} contexts for {B} prompts")
@@ -750,12 +863,18 @@ class DecodeEngine:
             nps[i] = max(1, min(nps[i], budget))
         t0 = time.perf_counter_ns()
         lps = None  # per row (logprobs, top_logprobs) or None
-        if self.backend == "torch":
+        self._last_spec = None
+        if self.backend == "torch" and self.speculative:
+            gen, t_pref, t_dec = self._generate_torch_spec(ids, nps, row_opts, drafts)
+            if on_tokens is not None:
+                on_tokens(gen)
+        elif self.backend == "torch":
             gen, t_pref, t_dec, lps = self._generate_torch(ids, nps, row_opts, want)
             if on_tokens is not None:
                 on_tokens(gen, lps) if lps is not None else on_tokens(gen)
         else:
-            gen, t_pref, t_dec, lps = self._generate_hip(ids, nps, row_opts, use_graph, on_tokens, want=want)
+            gen, t_pref, t_dec, lps = self._generate_hip(ids, nps, row_opts, use_graph, on_tokens, want=want,
+                                                         drafts=drafts)
         total = time.perf_counter_ns() - t0
         load = self.load_duration_ns if self._first_call else 0
         self._first_call = False
@@ -771,6 +890,9 @@ class DecodeEngine:
                                  total_duration_ns=total + load))
             if lps is not None and lps[i] is not None:
                 out[-1].logprobs, out[-1].top_logprobs = lps[i]
+            if self._last_spec is not None:
+                for k, v in self._last_spec[i].items():
+                    setattr(out[-1], k, v)
         return out
 
     def _read_logprobs(self, row: int, lo: int, hi: int, n: int):
@@ -784,12 +906,15 @@ class DecodeEngine:
         ti, tl = b["top_id"][row, lo:hi, :n].cpu().tolist(), b["top_lp"][row, lo:hi, :n].cpu().tolist()
         return lp, [list(zip(a, c)) for a, c in zip(ti, tl)]
 
-    def _generate_hip(self, ids, nps, row_opts, use_graph, on_tokens=None, check_every: int = 1, want=None):
+    def _generate_hip(self, ids, nps, row_opts, use_graph, on_tokens=None, check_every: int = 1, want=None,
+                      drafts=None):
         from .. import ops
 
         dev = self.device
         B = len(ids)
         with_lp = want is not None and any(w >= 0 for w in want)
+        spec = self.speculative > 0  # K + 1 rows per sequence and step: speculative graphs, done polled per chunk
+        spec_mode = int(drafts is not None)
         self._forget_slots(range(B))
         with torch.cuda.stream(self.stream):
             # ---- prefill: all prompt tokens except the last, in <=prefill_chunk-row chunks
@@ -808,12 +933,18 @@ class DecodeEngine:
             if with_lp:
                 self._lp_bufs()["topn"][:B].copy_(torch.tensor(want, dtype=torch.int32))
                 lq = self._lp_struct(True, max(want))
+            if spec:
+                self._spec_begin(range(B), range(B), ids, drafts)
             self.stream.synchronize()
             t1 = time.perf_counter_ns()
             steps = max(nps)
             stream_h = ctypes.c_void_p(self.stream.cuda_stream)
 
             def launch(nsteps: int) -> None:
+                if spec and not use_graph:
+                    for _ in range(nsteps):
+                        self._forward_spec(B, spec_mode)
+                    return
                 if not use_graph:
                     for _ in range(nsteps):
                         if lq is None:  # (the call it always was: wrappers of _forward see the same arguments)
@@ -822,13 +953,14 @@ class DecodeEngine:
                             self._forward(B, r, want_logits=True, want_sample=True, lp=lq)
                     return
                 k = self.steps_per_graph
-                g = self._graph(B, k, with_lp) if nsteps >= k else None
+                graph = (lambda n: self._graph_spec(B, n, spec_mode)) if spec else (lambda n: self._graph(B, n, with_lp))
+                g = graph(k) if nsteps >= k else None
                 for _ in range(nsteps // k):
                     rc = self.lib.cain_graph_launch(ctypes.c_void_p(g), stream_h)
                     if rc != 0:
                         raise RuntimeError(f"hipGraphLaunch failed rc={rc}")
                 if nsteps % k:
-                    g1 = self._graph(B, 1, with_lp)
+                    g1 = graph(1)
                     for _ in range(nsteps % k):
                         if self.lib.cain_graph_launch(ctypes.c_void_p(g1), stream_h) != 0:
                             raise RuntimeError("hipGraphLaunch failed")
@@ -839,7 +971,8 @@ class DecodeEngine:
             t_first = time.perf_counter_ns()
             done_steps = 1
             emitted = [0] * B
-            watch = on_tokens is not None or any(o["eos_id"] >= 0 or o["stop"] for o in row_opts)
+            # (speculative: a step commits up to K + 1 tokens, so rows finish in fewer steps than tokens)
+            watch = spec or on_tokens is not None or any(o["eos_id"] >= 0 or o["stop"] for o in row_opts)
             chunk = self.steps_per_graph * max(1, int(check_every))
 
             def emit(new, ng) -> None:
@@ -872,6 +1005,8 @@ class DecodeEngine:
                 emit([gen[i, emitted[i]: n_gen[i]].tolist() for i in range(B)], n_gen)
             lps = [self._read_logprobs(i, 0, n_gen[i], want[i]) if want[i] >= 0 else None
                    for i in range(B)] if with_lp else None
+            if spec:
+                self._last_spec = [self._spec_stats(i) for i in range(B)]
             t2 = time.perf_counter_ns()
         self.last_ttft_ns = t_first - t0
         return [gen[i, : n_gen[i]].tolist() for i in range(B)], t1 - t0, t2 - t1, lps
@@ -1015,6 +1150,41 @@ class DecodeEngine:
         t1 = time.perf_counter_ns()
         return gens, 0, t1 - t0, lps if with_lp else None
 
+    def _generate_torch_spec(self, ids, nps, row_opts, drafts=None):
+        """The oracle backend under the speculative rule (engine/speculative.py): per step the drafts of the host
+        rule, one oracle forward over the K + 1 rows, the host sampler per row, the host accept.  The random stream
+        is numpy's, one draw per sampled token, so each row samples from the generator state plain decoding has at
+        its generated index and the state is set back to the one after the last committed token."""
+        t0 = time.perf_counter_ns()
+        K, V = self.speculative, self.cfg.vocab
+        gens, stats = [], []
+        for i, p in enumerate(ids):
+            o = row_opts[i]
+            rng = np.random.default_rng(o["seed"])
+            given = drafts[i] if drafts is not None and drafts[i] is not None else None
+            st = SeqState(tok=p[-1], pos=len(p) - 1, max_new=nps[i], eos_id=o["eos_id"], stop=o["stop"], seq=list(p))
+            cache: list = []
+            fed = 0  # positions the cache holds
+            while not st.done:
+                dr = spec_draft_host(st.seq, st.pos, st.n_gen, K, self.T_max, st.max_new,
+                                     given=[] if drafts is not None and given is None else given, vocab=V)
+                step = torch.tensor([st.seq[fed: st.pos + 1] + dr], device=self.device)
+                logits = self.ref.forward(step, cache=cache)[0, -(len(dr) + 1):].float().cpu()
+                sampled, states = [], [rng.bit_generator.state]
+                for j in range(len(dr) + 1):
+                    sampled.append(sample_host(logits[j], st.gen + dr[:j], o, rng))
+                    states.append(rng.bit_generator.state)
+                c = st.commit_step(dr, sampled, self.T_max)
+                rng.bit_generator.state = states[c]
+                fed = st.pos
+                for li in range(len(cache)):  # rejected rows leave the cache
+                    cache[li] = [cache[li][0][:, :fed], cache[li][1][:, :fed]]
+            gens.append(list(st.gen))
+            stats.append(dict(draft_count=st.drafted, draft_accepted=st.accepted, decode_steps=len(st.step_tokens),
+                              step_tokens=list(st.step_tokens)))
+        self._last_spec = stats
+        return gens, 0, time.perf_counter_ns() - t0
+
 
 SAMPLE_TOPK_MAX = 256  # the kernels' top-k clamp (csrc/sample.hip SS_KMAX): top_k <= 0 or above it means this many
 SAMPLE_HIST = 64       # ids the repeat penalty can look back on (csrc/sample.hip HIST)
@@ -1124,6 +1294,8 @@ class ContinuousBatch:
         if k == 0:
             return []
         want = _want_logprobs(logprobs, top_logprobs, k)
+        if eng.speculative and any(w >= 0 for w in want):
+            raise ValueError("logprobs cannot be combined with speculative decoding")
         if k > len(self.free_slots):
             raise ValueError(f"{k} requests but only {len(self.free_slots)} free rows")
         ids = [eng.encode(p) or [eng.cfg.bos_id] for p in prompts]
@@ -1171,6 +1343,8 @@ class ContinuousBatch:
             eng.sample_params[ops.SAMPLE_BYTES * self.n: ops.SAMPLE_BYTES * (self.n + k)].copy_(ops.sample_params_tensor(row_opts, "cpu").to(eng.device))
             if eng._lp is not None or any(w >= 0 for w in want):
                 eng._lp_bufs()["topn"][sl].copy_(torch.tensor(want, dtype=torch.int32))
+            if eng.speculative:
+                eng._spec_begin(rows, slots, ids)
         self.want += want
         self.n += k
         self.row_slot += slots
@@ -1196,18 +1370,28 @@ class ContinuousBatch:
         for i in range(self.n):
             self._steps[i] += steps
         with_lp = any(w >= 0 for w in self.want)  # some live row wants logprobs: the graphs that compute them
+        # speculative engines: each step drafts (n-gram lookup), verifies K + 1 rows per live row and commits
+        graph = (lambda n: eng._graph_spec(self.n, n, 0)) if eng.speculative else \
+            (lambda n: eng._graph(self.n, n, with_lp))
         with torch.cuda.stream(eng.stream):
             k = eng.steps_per_graph
             if steps >= k:
-                g = eng._graph(self.n, k, with_lp)
+                g = graph(k)
                 for _ in range(steps // k):
                     if eng.lib.cain_graph_launch(ctypes.c_void_p(g), stream_h) != 0:
                         raise RuntimeError("hipGraphLaunch failed")
             if steps % k:
-                g1 = eng._graph(self.n, 1, with_lp)
+                g1 = graph(1)
                 for _ in range(steps % k):
                     if eng.lib.cain_graph_launch(ctypes.c_void_p(g1), stream_h) != 0:
                         raise RuntimeError("hipGraphLaunch failed")
+
+    def spec_stats(self, row: int) -> Optional[Dict]:
+        """Speculative counters of a live row (``GenResult``'s fields of that name); None when the mode is off."""
+        if not self.eng.speculative:
+            return None
+        with torch.cuda.stream(self.eng.stream):
+            return self.eng._spec_stats(row)
 
     def logprobs(self, row: int, lo: int = 0, hi: Optional[int] = None):
         """``(logprobs, top_logprobs)`` of tokens ``lo .. hi - 1`` (default: all polled so far) of a live row that
@@ -1285,6 +1469,9 @@ class ContinuousBatch:
                 if eng._lp is not None:
                     for key in ("topn", "lp", "top_id", "top_lp"):
                         eng._lp[key][dst] = eng._lp[key][src]
+                if eng._spec is not None:  # (the records are per slot and stay)
+                    for key in ("given", "drafted", "accepted", "n_step", "step_tokens"):
+                        eng._spec[key][dst] = eng._spec[key][src]
             for j, h in moves.items():
                 for lst in self._row_lists():
                     lst[h] = lst[j]

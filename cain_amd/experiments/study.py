@@ -168,6 +168,8 @@ class StudySettings:
     weights: str = "bf16"
     # on-device KV-cache storage: bf16, or fp8 (e4m3)
     kv: str = "bf16"
+    # on-device speculative decoding: n-gram drafts per decode step (0: off; the server's --speculative)
+    speculative: int = 0
     # weight storage of a "local:<device>" remote server ("" = the on-device arm's ``weights``: the reference's
     # Ollama served the same 4-bit builds in both arms)
     remote_weights: str = ""
@@ -407,6 +409,8 @@ class _StudyBase:
                 args += ["--weights", s.weights]
             if s.kv != "bf16":
                 args += ["--kv", s.kv]
+            if s.speculative and backend != "fake":
+                args += ["--speculative", str(s.speculative)]
             if s.trace:
                 args += ["--trace-dir", str(self.results_output_path / s.name / "traces" / f"rank{self.rank}")]
             env = {}

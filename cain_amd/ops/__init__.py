@@ -25,6 +25,8 @@ op                     source                      replaces (Ollama/llama.cpp)
 ``kv_copy_prefix``     csrc/kv_prefix.hip          a slot's cached prompt prefix copied to another slot
 ``sample``             csrc/sample.hip             repeat-penalty/temperature/top-k/top-p
 ``logprob_rows``       csrc/logprob.hip            log-softmax, top-n and token logprobs on device
+``spec_draft``         csrc/spec.hip               n-gram / given drafts -> K + 1 expanded rows per sequence
+``spec_accept``        csrc/spec.hip               commit the longest correct draft prefix (lookup decoding)
 ``Plan``               csrc/runtime.hip            per-step schedule + hipGraph replay
 =====================  ==========================  =============================
 """
@@ -957,3 +959,170 @@ def _sample_ws(device, nbytes: int) -> torch.Tensor:
     if t is None or t.numel() * 4 < nbytes:
         t = _SAMPLE_WS[device] = torch.zeros((nbytes + 3) // 4, device=device, dtype=torch.int32)
     return t
+
+
+# ------------------------------------------------------------ speculative decoding (csrc/spec.hip)
+SPEC_K_MAX = 7  # csrc/spec.h
+ROW_KEYS = ("tok", "pos", "slot", "n_gen", "max_new", "done", "hist")
+_SPEC_INTS = ("K", "mode", "slots", "lds", "ldv", "ldt", "vocab", "ldg")
+_SPEC_PTRS = ("seq", "given", "x_tok", "x_pos", "x_slot", "x_n_gen", "x_max_new", "x_done", "x_hist", "x_gen",
+              "x_params", "nd", "draft", "drafted", "accepted", "n_step", "step_tokens")
+
+
+class CainSpec(ctypes.Structure):  # csrc/spec.h CainSpec
+    _fields_ = [(n, ci) for n in _SPEC_INTS] + [(n, vp) for n in _SPEC_PTRS]
+
+
+def spec_alloc(R: int, K: int, slots: int, T_max: int, vocab: int, device) -> dict:
+    """Buffers of speculative decoding for up to ``R`` sequences with ``K`` drafts each (csrc/spec.h): the token
+    record per cache slot, the given drafts, the expanded row state of the ``R (K + 1)``-row verify forward, the
+    step's drafts and the per-sequence counters."""
+    if not 1 <= K <= SPEC_K_MAX:
+        raise ValueError(f"speculative K must be in 1..{SPEC_K_MAX}, got {K}")
+    X = R * (K + 1)
+    z = lambda *s, dt=torch.int32: torch.zeros(*s, device=device, dtype=dt)  # noqa: E731
+    return dict(K=int(K), vocab=int(vocab), seq=z(slots, T_max), given=torch.full((R, T_max), -1, device=device,
+                                                                                 dtype=torch.int32),
+                x_tok=z(X), x_pos=z(X), x_slot=torch.full((X,), -1, device=device, dtype=torch.int32), x_n_gen=z(X),
+                x_max_new=z(X), x_done=z(X), x_hist=z(X, 64), x_gen=z(X, T_max),
+                x_params=z(X * SAMPLE_BYTES, dt=torch.uint8), nd=z(R), draft=torch.full((R, K), -1, device=device,
+                                                                                      dtype=torch.int32),
+                drafted=z(R), accepted=z(R), n_step=z(R), step_tokens=z(R, T_max))
+
+
+def spec_struct(spec: dict, mode: int) -> CainSpec:
+    """The kernels' view of ``spec_alloc`` buffers; ``mode`` 0: n-gram drafts, 1: the ``given`` drafts."""
+    s = CainSpec()
+    s.K, s.mode, s.vocab = int(spec["K"]), int(mode), int(spec["vocab"])
+    s.slots, s.lds = spec["seq"].shape[0], spec["seq"].stride(0)
+    s.ldv, s.ldt, s.ldg = spec["given"].stride(0), spec["step_tokens"].stride(0), spec["x_gen"].stride(0)
+    for k in _SPEC_PTRS:
+        setattr(s, k, spec[k].data_ptr())
+    return s
+
+
+def _spec_sig(lib) -> None:
+    if getattr(lib, "_cain_spec_sig", False):
+        return
+    lib.cain_spec_draft.argtypes = [vp, ci, ci] + [vp] * 9
+    lib.cain_spec_accept.argtypes = [vp, ci, ci] + [vp] * 8 + [ci, vp, vp]
+    lib.cain_plan_forward_spec.argtypes = [vp, ci, vp, vp, vp]
+    lib.cain_plan_capture_spec.restype = vp
+    lib.cain_plan_capture_spec.argtypes = [vp, ci, vp, vp, ci, vp, ctypes.POINTER(ci)]
+    if int(lib.cain_spec_size()) != ctypes.sizeof(CainSpec):
+        raise NativeOpsUnavailable(f"{LIB_PATH}: CainSpec is {int(lib.cain_spec_size())} bytes, this package packs "
+                                   f"{ctypes.sizeof(CainSpec)}: rebuild (python -m cain_amd.build)")
+    lib._cain_spec_sig = True
+
+
+def load_spec() -> ctypes.CDLL:
+    """``load()`` with the speculative entry points' signatures set (a library without them: AttributeError)."""
+    lib = load()
+    _spec_sig(lib)
+    return lib
+
+
+def spec_draft(rows: dict, params: torch.Tensor, spec: dict, R: int, mode: int, T_max: int) -> None:
+    """Draft for sequences ``[0, R)`` of the decode rows (``ROW_KEYS`` tensors) and write the expanded state."""
+    lib = load_spec()
+    _gpu(params, *[rows[k] for k in ROW_KEYS])
+    assert spec["nd"].shape[0] >= R and rows["tok"].shape[0] >= R
+    s = spec_struct(spec, mode)
+    _check(lib.cain_spec_draft(ctypes.byref(s), R, T_max, *[_p(rows[k]) for k in ROW_KEYS], _p(params), _stream()),
+           "spec_draft")
+
+
+def spec_accept(rows: dict, gen: torch.Tensor, params: torch.Tensor, spec: dict, R: int, T_max: int) -> None:
+    """Commit, per sequence, the tokens the sampler left in ``spec["x_tok"]`` that the step's drafts allow."""
+    lib = load_spec()
+    _gpu(params, gen, *[rows[k] for k in ROW_KEYS])
+    s = spec_struct(spec, 0)
+    r = rows
+    _check(lib.cain_spec_accept(ctypes.byref(s), R, T_max, _p(r["tok"]), _p(r["pos"]), _p(r["slot"]), _p(r["n_gen"]),
+                                _p(r["max_new"]), _p(r["done"]), _p(r["hist"]), _p(gen), gen.stride(0), _p(params),
+                                _stream()), "spec_accept")
+
+
+def _np(t):
+    import numpy as np
+
+    return np.array(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+
+
+def spec_draft_ref(rows: dict, params, spec: dict, R: int, mode: int, T_max: int) -> dict:
+    """``spec_draft`` from the rule (engine/speculative.py), sequence by sequence in Python: returns the numpy
+    arrays the kernel writes (``x_*`` over the first ``R (K + 1)`` rows, ``nd``, ``draft``)."""
+    import numpy as np
+
+    from ..engine import speculative as sp
+
+    K = int(spec["K"])
+    K1 = K + 1
+    r = {k: _np(rows[k]) for k in ROW_KEYS}
+    hist = r["hist"].reshape(-1, 64)
+    par = _np(params).reshape(-1, SAMPLE_BYTES)
+    seq, given = _np(spec["seq"]), _np(spec["given"])
+    out = dict(x_tok=np.zeros(R * K1, np.int32), x_pos=np.zeros(R * K1, np.int32),
+               x_slot=np.full(R * K1, -1, np.int32), x_n_gen=np.zeros(R * K1, np.int32),
+               x_max_new=np.zeros(R * K1, np.int32), x_done=np.zeros(R * K1, np.int32),
+               x_hist=np.zeros((R * K1, 64), np.int32), x_params=np.zeros((R * K1, SAMPLE_BYTES), np.uint8),
+               nd=np.zeros(R, np.int32), draft=np.full((R, K), -1, np.int32))
+    for i in range(R):
+        sl, pos, ng = int(r["slot"][i]), int(r["pos"][i]), int(r["n_gen"][i])
+        dr = sp.draft(seq[sl] if 0 <= sl < seq.shape[0] else [], pos, ng, K, T_max, int(r["max_new"][i]),
+                      done=bool(r["done"][i]), slot=sl, given=given[i] if mode == 1 else None,
+                      vocab=int(spec["vocab"]))
+        d = len(dr)
+        out["nd"][i] = d
+        out["draft"][i, :d] = dr
+        for j in range(K1):
+            x = i * K1 + j
+            out["x_params"][x] = par[i]
+            out["x_hist"][x] = sp.draft_ring(hist[i], ng, dr, j) if j <= d else hist[i]
+            if j == 0:
+                vals = (r["tok"][i], pos, sl, ng, r["max_new"][i], r["done"][i])
+            elif j <= d:
+                vals = (dr[j - 1], pos + j, sl, ng + j, sp.NO_BUDGET, 0)
+            else:
+                vals = (0, 0, -1, 0, 0, 0)
+            for k, v in zip(("x_tok", "x_pos", "x_slot", "x_n_gen", "x_max_new", "x_done"), vals):
+                out[k][x] = v
+    return out
+
+
+def spec_accept_ref(rows: dict, gen, params, spec: dict, R: int, T_max: int) -> dict:
+    """``spec_accept`` from the rule, sequence by sequence in Python: returns numpy copies of everything the kernel
+    may write (the decode rows, ``gen``, ``seq`` and the counters) after the step."""
+    import numpy as np
+
+    from ..engine import speculative as sp
+
+    K = int(spec["K"])
+    K1 = K + 1
+    out = {k: _np(rows[k]) for k in ROW_KEYS}
+    out["hist"] = out["hist"].reshape(-1, 64)
+    out["gen"] = _np(gen)
+    for k in ("seq", "drafted", "accepted", "n_step", "step_tokens"):
+        out[k] = _np(spec[k])
+    par = np.ascontiguousarray(_np(params).reshape(-1, SAMPLE_BYTES)).view(np.dtype(SAMPLE_DTYPE, align=True))[:, 0]
+    xt, nd, draft = _np(spec["x_tok"]), _np(spec["nd"]), _np(spec["draft"]).reshape(-1, K)
+    for i in range(R):
+        sl, ng = int(out["slot"][i]), int(out["n_gen"][i])
+        if sl < 0 or out["done"][i]:
+            continue
+        st = sp.SeqState(tok=int(out["tok"][i]), pos=int(out["pos"][i]), max_new=int(out["max_new"][i]),
+                         eos_id=int(par[i]["eos_id"]), stop=[int(s) for s in par[i]["stop"]], slot=sl, n_gen=ng,
+                         gen=list(out["gen"][i, :ng]), hist=list(out["hist"][i]),
+                         seq=list(out["seq"][sl, :int(out["pos"][i]) + 1]))
+        d = int(nd[i])
+        c = st.commit_step(list(draft[i, :d]), list(xt[i * K1: i * K1 + d + 1]), T_max)
+        out["gen"][i, ng: ng + c] = st.gen[ng:]
+        out["hist"][i] = st.hist
+        out["seq"][sl, : len(st.seq)] = st.seq
+        out["tok"][i], out["pos"][i], out["n_gen"][i], out["done"][i] = st.tok, st.pos, st.n_gen, int(st.done)
+        out["drafted"][i] += d
+        out["accepted"][i] += c - 1
+        k = int(out["n_step"][i])
+        out["step_tokens"][i, k % out["step_tokens"].shape[1]] = c
+        out["n_step"][i] = k + 1
+    return out

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common.h"
+#include "spec.h"
 
 constexpr int CAIN_MAX_ROWS = 256;  // rows per forward (decode batch / prefill chunk)
 
@@ -88,6 +89,12 @@ CAIN_API int cain_logprob_pre(const float* logits, int ldl, int V, int M, const 
                               float* top_lp, void* keep, hipStream_t st);
 CAIN_API int cain_logprob_chosen(const float* logits, int ldl, int V, int M, const int* gen, int ldg, const void* keep,
                                  float* lp, hipStream_t st);
+CAIN_API int cain_spec_draft(const CainSpec* s, int R, int T_max, const int* tok, const int* pos, const int* slot,
+                             const int* n_gen, const int* max_new, const int* done, const int* hist,
+                             const void* params, hipStream_t st);
+CAIN_API int cain_spec_accept(const CainSpec* s, int R, int T_max, int* tok, int* pos, const int* slot, int* n_gen,
+                              const int* max_new, int* done, int* hist, int* gen, int ldg, const void* params,
+                              hipStream_t st);
 
 extern "C" {
 
@@ -354,6 +361,26 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
   return 0;
 }
 
+// One speculative decode step over R sequences (spec.hip): draft into the expanded state, verify with the ordinary
+// forward over R (K + 1) rows -- logits and the ordinary sampler on the expanded rows -- then commit what matched.
+int forward_spec(const Plan& p, int R, const CainRows& r, const CainSpec& s, hipStream_t st) {
+  const int T = p.d.T_max;
+  CK(cain_spec_draft(&s, R, T, r.tok, r.pos, r.slot, r.n_gen, r.max_new, r.done, r.hist, r.sample_params, st));
+  CainRows x{};
+  x.tok = s.x_tok, x.pos = s.x_pos, x.slot = s.x_slot, x.n_gen = s.x_n_gen, x.max_new = s.x_max_new;
+  x.done = s.x_done, x.hist = s.x_hist, x.gen = s.x_gen, x.ldg = s.ldg, x.sample_params = s.x_params;
+  CK(forward(p, R * (s.K + 1), x, 1, 1, st));
+  CK(cain_spec_accept(&s, R, T, r.tok, r.pos, r.slot, r.n_gen, r.max_new, r.done, r.hist, r.gen, r.ldg,
+                      r.sample_params, st));
+  return 0;
+}
+
+bool spec_rows_ok(const Plan& p, int R, const CainRows* r, const CainSpec* s) {
+  if (!r || !s || R < 1 || s->K < 1 || s->K > SPEC_K_MAX) return false;
+  if (!r->n_gen || !r->max_new || !r->done || !r->hist || !r->gen || !r->sample_params) return false;
+  return R * (s->K + 1) <= max_rows(p.d) && s->vocab <= p.d.V;
+}
+
 }  // namespace
 
 extern "C" {
@@ -439,6 +466,48 @@ CAIN_API void* cain_plan_capture_lp(void* plan, int M, const CainRows* rows, int
 
 CAIN_API void* cain_plan_capture(void* plan, int M, const CainRows* rows, int steps, hipStream_t st, int* err) {
   return cain_plan_capture_lp(plan, M, rows, steps, nullptr, st, err);
+}
+
+// Speculative decoding: one step (draft -> forward over R (K + 1) expanded rows -> accept) over the R sequences of
+// `rows`; -1 when R (K + 1) exceeds the rows a forward of this plan may have.
+CAIN_API int cain_plan_forward_spec(void* plan, int R, const CainRows* rows, const CainSpec* spec, hipStream_t st) {
+  auto* p = static_cast<Plan*>(plan);
+  g_fail[0] = 0;
+  if (!spec_rows_ok(*p, R, rows, spec)) return -1;
+  return forward_spec(*p, R, *rows, *spec, st);
+}
+
+// `steps` such steps in one graph.
+CAIN_API void* cain_plan_capture_spec(void* plan, int R, const CainRows* rows, const CainSpec* spec, int steps,
+                                      hipStream_t st, int* err) {
+  auto* p = static_cast<Plan*>(plan);
+  *err = 0;
+  if (!spec_rows_ok(*p, R, rows, spec) || steps < 1) {
+    *err = -1;
+    return nullptr;
+  }
+  hipGraph_t g = nullptr;
+  hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+  if (e != hipSuccess) {
+    *err = int(e);
+    return nullptr;
+  }
+  int fe = 0;
+  for (int s = 0; s < steps && fe == 0; ++s) fe = forward_spec(*p, R, *rows, *spec, st);
+  e = hipStreamEndCapture(st, &g);
+  if (fe != 0 || e != hipSuccess) {
+    *err = fe ? fe : int(e);
+    if (g) (void)hipGraphDestroy(g);
+    return nullptr;
+  }
+  hipGraphExec_t ex = nullptr;
+  e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (e != hipSuccess) {
+    *err = int(e);
+    return nullptr;
+  }
+  return ex;
 }
 
 CAIN_API int cain_graph_launch(void* exec, hipStream_t st) {

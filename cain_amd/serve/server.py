@@ -171,9 +171,14 @@ class EngineBackend(Backend):
     def __init__(self, models: List[str], device: str = "cuda:0", max_batch: int = 16, max_context: int = 2048,
                  backend: Optional[str] = None, seed: int = 0, preload: bool = False, steps_per_graph: int = 8,
                  trace_dir: Optional[str] = None, weight_dtype: str = "bf16", continuous: bool = True,
-                 kv_dtype: str = "bf16", prefix_cache: bool = False):
+                 kv_dtype: str = "bf16", prefix_cache: bool = False, speculative: int = 0):
         self._models = list(models)
         self.prefix_cache = bool(prefix_cache)
+        self.speculative = int(speculative)  # drafts per decode step (engine/speculative.py); 0: off
+        if not 0 <= self.speculative <= 7:
+            raise ValueError(f"speculative must be in 0..7, got {speculative}")
+        if self.speculative and self.prefix_cache:
+            raise ValueError("speculative decoding and prefix_cache cannot be combined")
         self.kv_dtype = kv_dtype
         # continuous batching needs the HIP engine; tracing records whole static batches
         self.continuous = continuous and not trace_dir
@@ -209,7 +214,8 @@ class EngineBackend(Backend):
                 eng = DecodeEngine(model, device=self.device, max_batch=self._max_batch,
                                    max_context=self.max_context, backend=self.backend, seed=self.seed,
                                    steps_per_graph=self.steps_per_graph, weight_dtype=self.weight_dtype,
-                                   kv_dtype=self.kv_dtype, prefix_cache=self.prefix_cache)
+                                   kv_dtype=self.kv_dtype, prefix_cache=self.prefix_cache,
+                                   speculative=self.speculative)
                 self.engines[model] = eng
             return eng
 
@@ -247,6 +253,8 @@ class EngineBackend(Backend):
                            "parameter_size": f"{cfg.n_params() / 1e9:.1f}B",
                            "quantization_level": QUANT_LEVEL[self.weight_dtype], "format": "cain-packed"},
                "model_info": info}
+        if self.speculative:
+            out["details"]["speculative"] = f"ngram-k{self.speculative}"
         if ckpt:  # as Ollama's show: the prompt template and the stop tokens (a checkpoint's)
             from ..models.hf import load_tokenizer
 
@@ -390,7 +398,8 @@ class EngineBackend(Backend):
             j.result = GenResult(model, list(cb.prompt_tokens[r]), toks, tok.decode(toks), reason,
                                  load_duration_ns=0, prompt_eval_duration_ns=int(st["t_pre"] - st["t0"]),
                                  eval_duration_ns=int(now - st["t_pre"]),
-                                 total_duration_ns=int(now - j.t_submit * 1e9), prompt_cached=int(cb.reused[r]))
+                                 total_duration_ns=int(now - j.t_submit * 1e9), prompt_cached=int(cb.reused[r]),
+                                 **(cb.spec_stats(r) or {}))
             j.ttft_ns = int(st["t_first"] - st["t0"])
             j.done.set()
         if done_rows:
@@ -578,7 +587,9 @@ class OllamaHandler(BaseHTTPRequestHandler):
         elif self.path == "/api/ps":
             be = self.scheduler.backend
             self._send_json(200, {"models": [{"name": m, "model": m, "expires_at": "2999-01-01T00:00:00Z",
-                                              "prefix_cache": bool(getattr(be, "prefix_cache", False))}
+                                              "prefix_cache": bool(getattr(be, "prefix_cache", False)),
+                                              **({"speculative": f"ngram-k{be.speculative}"}
+                                                 if getattr(be, "speculative", 0) else {})}
                                              for m in self.scheduler.queues]})
         else:
             self._send_json(404, {"error": "not found"})
@@ -635,6 +646,9 @@ class OllamaHandler(BaseHTTPRequestHandler):
             return self._send_json(400, {"error": "top_logprobs needs logprobs: true"})
         if want_lp and not getattr(self.scheduler.backend, "logprobs", False):
             return self._send_json(400, {"error": "logprobs: no model behind this backend"})
+        if want_lp and getattr(self.scheduler.backend, "speculative", 0):
+            return self._send_json(400, {"error": "logprobs cannot be combined with speculative decoding "
+                                                  "(--speculative)"})
         opts = dict(body.get("options") or {})
         n = opts.get("num_predict")
         # the length policy reads the user's words ("In N words ..."), not the template around them
@@ -757,6 +771,10 @@ def main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--prefix-cache", action="store_true",
                     help="keep each cache slot's tokens between requests and prefill only what differs from the best "
                          "matching slot (continuous batching on the HIP engine); responses carry 'context'")
+    ap.add_argument("--speculative", type=int, default=0, metavar="K",
+                    help="speculative decoding: K (1..7) n-gram drafts from the request's own tokens per decode step, "
+                         "verified K + 1 rows per weight pass; the tokens are plain decoding's (not with "
+                         "--prefix-cache or logprobs)")
     ap.add_argument("--checkpoint", action="append", metavar="TAG=PATH",
                     help="serve a Hugging Face checkpoint directory or GGUF file under TAG (repeatable; models/hf.py); "
                          "PATH 'ollama' takes the blob a local Ollama store keeps for TAG")
@@ -768,12 +786,17 @@ def main(argv: Optional[List[str]] = None) -> None:
     for m in models:
         if m not in MODELS and m not in TINY and m not in ck_tags:
             raise SystemExit(f"unknown model {m}")
+    if not 0 <= ns.speculative <= 7:
+        raise SystemExit("--speculative must be in 0..7")
+    if ns.speculative and ns.prefix_cache:
+        raise SystemExit("--speculative and --prefix-cache cannot be combined")
     if ns.backend == "fake":
         be: Backend = FakeBackend(models, tokens_per_s=ns.fake_tok_s, prefill_s=ns.fake_prefill_s)
     else:
         be = EngineBackend(models, device=ns.device, max_batch=ns.max_batch, max_context=ns.max_context,
                            backend=ns.backend, preload=ns.preload, trace_dir=ns.trace_dir, weight_dtype=ns.weights,
-                           continuous=not ns.static_batching, kv_dtype=ns.kv, prefix_cache=ns.prefix_cache)
+                           continuous=not ns.static_batching, kv_dtype=ns.kv, prefix_cache=ns.prefix_cache,
+                           speculative=ns.speculative)
     srv = make_server(be, ns.host, ns.port, ns.batch_window_ms, ns.verbose)
     print(f"[serve] Ollama-compatible API on http://{ns.host}:{srv.server_address[1]} models={models}", flush=True)
     try:
@@ -794,10 +817,12 @@ def generate_main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--weights", choices=list(QUANT_LEVEL), default="bf16")
     ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16")
     ap.add_argument("--checkpoint", metavar="PATH", help="a Hugging Face checkpoint directory, served as --model")
+    ap.add_argument("--speculative", type=int, default=0, metavar="K", help="speculative decoding with K n-gram drafts")
     ns = ap.parse_args(argv)
     if ns.checkpoint:
         register_checkpoints([f"{ns.model}={ns.checkpoint}"])
-    be = EngineBackend([ns.model], device=ns.device, max_batch=1, weight_dtype=ns.weights, kv_dtype=ns.kv)
+    be = EngineBackend([ns.model], device=ns.device, max_batch=1, weight_dtype=ns.weights, kv_dtype=ns.kv,
+                       speculative=ns.speculative)
     opts = {k: v for k, v in (("temperature", ns.temperature), ("seed", ns.seed)) if v is not None}
     job = Job(ns.model, ns.prompt, ns.num_predict or default_num_predict(ns.prompt), opts)
     be.run(ns.model, [job])
