@@ -52,6 +52,15 @@ class NativeOpsUnavailable(RuntimeError):
     pass
 
 
+class CainGemm(ctypes.Structure):
+    """The call record of every GEMM entry (csrc/cain_api.h CainGemm, which says what each entry reads)."""
+    _fields_ = ([(f, ctypes.c_void_p) for f in ("W", "sc", "dd", "gain", "xs", "X", "Y", "bias", "slot", "pos", "cos_t",
+                                                "sin_t", "kc", "vtc", "ws")]
+                + [("ws_bytes", ctypes.c_longlong)]
+                + [(f, ctypes.c_int) for f in ("ldx", "K", "N", "M", "ldy", "norm")] + [("eps", ctypes.c_float)]
+                + [(f, ctypes.c_int) for f in ("H", "Hkv", "hd", "T_max", "epi", "fmt", "tile0", "waves")])
+
+
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()
 
@@ -81,16 +90,12 @@ def load() -> ctypes.CDLL:
         if int(real.cain_sample_params_size()) != SAMPLE_BYTES:  # also an A/B build from an older source
             raise NativeOpsUnavailable(f"{LIB_PATH} packs {int(real.cain_sample_params_size())}-byte sampling "
                                        f"options, this package {SAMPLE_BYTES}: rebuild (python -m cain_amd.build)")
-        lib.cain_skinny_gemm_ex.argtypes = ([vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp, vp]
-                                            + [ci] * 6 + [vp])
-        lib.cain_gemm.argtypes = ([vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp, vp]
-                                  + [ci] * 4 + [vp, ctypes.c_longlong, ci, ci, vp])
-        lib.cain_gemm_w8.argtypes = ([vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp, vp]
-                                     + [ci] * 5 + [vp])
-        lib.cain_gemm_w4.argtypes = ([vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp, vp]
-                                     + [ci] * 5 + [vp])
-        lib.cain_gemm_w4_ex.argtypes = ([vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp, vp]
-                                        + [ci] * 4 + [vp, ctypes.c_longlong, ci, vp])
+        # (a build from before the record has no GEMM entry of these names: plan-level A/B runs only)
+        if hasattr(real, "cain_gemm_size") and int(real.cain_gemm_size()) != ctypes.sizeof(CainGemm):
+            raise NativeOpsUnavailable(f"{LIB_PATH} takes a {int(real.cain_gemm_size())}-byte GEMM call record, this "
+                                       f"package fills {ctypes.sizeof(CainGemm)}: rebuild (python -m cain_amd.build)")
+        for entry in ("bf16", "fp8", "mxfp4", "gguf", "fp8a8", "mxfp4a8"):
+            getattr(lib, "cain_gemm_" + entry).argtypes = [ctypes.POINTER(CainGemm), vp]
         lib.cain_gemm_w4_ws_bytes.restype = ctypes.c_longlong
         lib.cain_gemm_w4_ws_bytes.argtypes = [ci, ci, ci]
         lib.cain_gemm_w4_split.argtypes = [ci, ci, ci, ci, ctypes.c_longlong]
@@ -99,11 +104,7 @@ def load() -> ctypes.CDLL:
         lib.cain_gemm_w4_set_split_min_quads.argtypes = [ci]
         lib.cain_gemm_w4_set_variant.argtypes = [ci]
         lib.cain_wgemm_set_inline.argtypes = [ci]
-        lib.cain_gemm_q4.argtypes = ([ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp,
-                                      vp] + [ci] * 5 + [vp])
         lib.cain_gemm_q4_rows.argtypes = [ci, ci]
-        lib.cain_gemm_q6.argtypes = ([ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, ci, cf, vp, vp, vp, vp, vp,
-                                      vp] + [ci] * 6 + [vp])
         lib.cain_gemm_q6_rows.argtypes = [ci, ci]
         lib.cain_gemm_q_set_tile.argtypes = [ci]
         lib.cain_gemm_q_set_tile.restype = None
@@ -114,10 +115,7 @@ def load() -> ctypes.CDLL:
         lib.cain_wgemm_get_inline.argtypes = []
         lib.cain_gemm_w4_variant.argtypes = [ci, ci, ci, ci]
         lib.cain_gemm_w4_set_occupancy.argtypes = [ci]
-        lib.cain_gemm_w8a8.argtypes = ([vp, vp, vp, ci, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
-                                       + [ci] * 4 + [vp, ctypes.c_longlong, ci, vp])
         lib.cain_quant_rows.argtypes = [vp, ci, ci, ci, vp, ci, vp, ci, cf, vp]
-        lib.cain_gemm_w4a8.argtypes = lib.cain_gemm_w8a8.argtypes
         lib.cain_w4a8_set_min_rows.argtypes = [ci]
         lib.cain_w8a8_eligible.argtypes = [ci, ci, ci]
         lib.cain_w8a8_ws_bytes.restype = ctypes.c_longlong
@@ -292,13 +290,35 @@ def _workspace(device, nbytes: int) -> Optional[torch.Tensor]:
     return ws
 
 
-def _gemm_call(lib, wp, x, K, n, M, out, bias, norm, eps, slot, pos, cos_t, sin_t, kc, vtc, H, Hkv, hd, T_max, epi,
-               waves, batched: bool):
-    nbytes = gemm_ws_bytes(n, K, M) if batched else 0
-    ws = _workspace(x.device, nbytes)
-    return lib.cain_gemm(_p(wp), _p(x), x.stride(0), K, n, M, _p(out), out.stride(0), _p(bias), int(bool(norm)), eps,
-                         _p(slot), _p(pos), _p(cos_t), _p(sin_t), _p(kc), _p(vtc), H, Hkv, hd, T_max, _p(ws),
-                         nbytes, epi, waves, _stream())
+def _gemm_record(w, sc, x, n: int, epi: int, bias, out, norm: bool, eps: float, rope, n_out: Optional[int] = None):
+    """The call record of y[M, n_out] = epi(x @ w^T) and ``out``: checked (``EPI_RESID`` updates it in place) or
+    allocated; ``rope``: the ``EPI_QKV_ROPE`` arguments, an 8-bit cache (``is_fp8_cache``) sets ``EPI_KV_FP8``."""
+    M, K = x.shape
+    if n_out is None:
+        n_out = n // 2 if epi in (EPI_SILU, EPI_GELU) else n
+    if epi == EPI_RESID:
+        assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
+    if epi == EPI_QKV_ROPE:
+        assert rope is not None, "EPI_QKV_ROPE needs the rope/cache arguments"
+    if out is None:
+        out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
+    r = rope or {}
+    if rope and is_fp8_cache(r["kc"]):
+        epi |= EPI_KV_FP8
+    g = CainGemm(W=_p(w), sc=_p(sc), X=_p(x), ldx=x.stride(0), K=K, N=n, M=M, Y=_p(out), ldy=out.stride(0),
+                 bias=_p(bias), norm=int(bool(norm)), eps=eps, slot=_p(r.get("slot")), pos=_p(r.get("pos")),
+                 cos_t=_p(r.get("cos_t")), sin_t=_p(r.get("sin_t")), kc=_p(r.get("kc")),
+                 vtc=_p(r.get("vtc")), H=r.get("H", 0), Hkv=r.get("Hkv", 0), hd=r.get("hd", 0),
+                 T_max=r["kc"].shape[-2] if rope else 0, epi=epi)
+    return g, out
+
+
+def _gemm_bf16(g: CainGemm, device, waves: int, batched: bool) -> int:
+    g.waves = waves
+    g.ws_bytes = gemm_ws_bytes(g.N, g.K, g.M) if batched else 0
+    ws = _workspace(device, g.ws_bytes)
+    g.ws = _p(ws)
+    return load().cain_gemm_bf16(g, _stream())
 
 
 def skinny_gemm(wp: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16, bias=None,
@@ -311,19 +331,12 @@ def skinny_gemm(wp: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16, 
     ``EPI_RESID``: ``out`` is the residual stream, updated in place.
     ``batched``: 16 < M <= 64 runs the LDS-staged split-K kernel (False forces the skinny kernel).
     """
-    lib = load()
     _gpu(wp, x)
     M, K = x.shape
     assert x.dtype == torch.bfloat16 and x.stride(1) == 1
     assert wp.shape[1] * 32 == K and wp.shape[0] * 16 == n, (tuple(wp.shape), K, n)
-    n_out = n // 2 if epi in (EPI_SILU, EPI_GELU) else n
-    if epi == EPI_RESID:
-        assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
-    if out is None:
-        out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
-    rc = _gemm_call(lib, wp, x, K, n, M, out, bias, norm, eps, None, None, None, None, None, None, 0, 0, 0, 0, epi,
-                    waves, batched)
-    _check(rc, "skinny_gemm")
+    g, out = _gemm_record(wp, None, x, n, epi, bias, out, norm, eps, None)
+    _check(_gemm_bf16(g, x.device, waves, batched), "skinny_gemm")
     return out
 
 
@@ -336,13 +349,9 @@ def qkv_rope(wp, x, n, q_out, kc, vtc, slot, pos, cos_t, sin_t, H, Hkv, hd, bias
              eps: float = 1e-6, waves: int = 0, batched: bool = True) -> None:
     """Fused QKV projection (+RMSNorm, +bias) -> RoPE -> Q buffer / K cache / V^T cache.  8-bit caches
     (``is_fp8_cache``) receive e4m3 elements (EPI_KV_FP8)."""
-    lib = load()
-    M, K = x.shape
-    T_max = kc.shape[-2]
-    epi = EPI_QKV_ROPE | (EPI_KV_FP8 if is_fp8_cache(kc) else 0)
-    rc = _gemm_call(lib, wp, x, K, n, M, q_out, bias, norm, eps, slot, pos, cos_t, sin_t, kc, vtc, H, Hkv, hd,
-                    T_max, epi, waves, batched)
-    _check(rc, "qkv_rope")
+    rope = dict(kc=kc, vtc=vtc, slot=slot, pos=pos, cos_t=cos_t, sin_t=sin_t, H=H, Hkv=Hkv, hd=hd)
+    g, _ = _gemm_record(wp, None, x, n, EPI_QKV_ROPE, bias, q_out, norm, eps, rope)
+    _check(_gemm_bf16(g, x.device, waves, batched), "qkv_rope")
 
 
 def gemm_w8(wq: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16, bias=None,
@@ -358,23 +367,9 @@ def gemm_w8(wq: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, n: int, epi:
     assert x.dtype == torch.bfloat16 and x.stride(1) == 1 and 1 <= M <= 64
     assert wq.dtype == torch.uint8 and wq.shape[0] * 16 == n and wq.shape[1] * 64 == K, (tuple(wq.shape), K, n)
     assert scale.dtype == torch.float32 and scale.numel() == n
-    n_out = n // 2 if epi in (EPI_SILU, EPI_GELU) else n
-    if epi == EPI_RESID:
-        assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
-    if out is None:
-        out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
-    r = rope or {}
-    if epi == EPI_QKV_ROPE:
-        assert rope is not None, "EPI_QKV_ROPE needs the rope/cache arguments"
-    T_max = r["kc"].shape[-2] if rope else 0
-    if rope and is_fp8_cache(r["kc"]):
-        epi |= EPI_KV_FP8
-    _cmax_set(lib, cmax, epi)
-    rc = lib.cain_gemm_w8(_p(wq), _p(scale), _p(x), x.stride(0), K, n, M, _p(out), out.stride(0), _p(bias),
-                          int(bool(norm)), eps, _p(r.get("slot")), _p(r.get("pos")), _p(r.get("cos_t")),
-                          _p(r.get("sin_t")), _p(r.get("kc")), _p(r.get("vtc")), r.get("H", 0), r.get("Hkv", 0),
-                          r.get("hd", 0), T_max, epi, _stream())
-    _check(rc, "gemm_w8")
+    g, out = _gemm_record(wq, scale, x, n, epi, bias, out, norm, eps, rope)
+    _cmax_set(lib, cmax, g.epi)
+    _check(lib.cain_gemm_fp8(g, _stream()), "gemm_w8")
     _cmax_check(lib, cmax)
     return out
 
@@ -391,25 +386,12 @@ def gemm_w4(wq: torch.Tensor, wsc: torch.Tensor, x: torch.Tensor, n: int, epi: i
     assert x.dtype == torch.bfloat16 and x.stride(1) == 1 and 1 <= M <= 64
     assert wq.dtype == torch.uint8 and wq.shape[0] * 16 == n and wq.shape[1] * 128 == K, (tuple(wq.shape), K, n)
     assert wsc.dtype == torch.uint8 and wsc.numel() * 32 == n * K
-    n_out = n // 2 if epi in (EPI_SILU, EPI_GELU) else n
-    if epi == EPI_RESID:
-        assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
-    if out is None:
-        out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
-    r = rope or {}
-    if epi == EPI_QKV_ROPE:
-        assert rope is not None, "EPI_QKV_ROPE needs the rope/cache arguments"
-    T_max = r["kc"].shape[-2] if rope else 0
-    if rope and is_fp8_cache(r["kc"]):
-        epi |= EPI_KV_FP8
-    nb = int(lib.cain_gemm_w4_ws_bytes(n, K, M))
-    ws = _w4_ws(x.device, nb)
-    _cmax_set(lib, cmax, epi)
-    rc = lib.cain_gemm_w4_ex(_p(wq), _p(wsc), _p(x), x.stride(0), K, n, M, _p(out), out.stride(0), _p(bias),
-                             int(bool(norm)), eps, _p(r.get("slot")), _p(r.get("pos")), _p(r.get("cos_t")),
-                             _p(r.get("sin_t")), _p(r.get("kc")), _p(r.get("vtc")), r.get("H", 0), r.get("Hkv", 0),
-                             r.get("hd", 0), T_max, _p(ws), nb, epi, _stream())
-    _check(rc, "gemm_w4")
+    g, out = _gemm_record(wq, wsc, x, n, epi, bias, out, norm, eps, rope)
+    g.ws_bytes = int(lib.cain_gemm_w4_ws_bytes(n, K, M))
+    ws = _w4_ws(x.device, g.ws_bytes)
+    g.ws = _p(ws)
+    _cmax_set(lib, cmax, g.epi)
+    _check(lib.cain_gemm_mxfp4(g, _stream()), "gemm_w4")
     _cmax_check(lib, cmax)
     return out
 
@@ -443,29 +425,17 @@ def _gemm_q(fmt: int, wq, sbuf, x, n: int, epi: int, bias, out, norm: bool, eps:
     if fmt == 2:
         assert epi in (EPI_BF16, EPI_RESID, EPI_F32, EPI_QKV_ROPE), "gemm_q6 has no gate/up activation epilogue"
     n_out = n // 2 if epi in (EPI_SILU, EPI_GELU) else 16 * tile0 + n
-    if epi == EPI_RESID:
-        assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
     if epi == EPI_QKV_ROPE and fmt == 2:
         assert rope is not None and out is not None, "EPI_QKV_ROPE needs the rope/cache arguments and the q rows"
-    elif epi == EPI_QKV_ROPE:
-        assert rope is not None, "EPI_QKV_ROPE needs the rope/cache arguments"
-    if out is None:
-        out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
-    elif fmt == 2 and epi != EPI_QKV_ROPE:
+    elif out is not None and fmt == 2:
         assert out.shape[1] >= n_out
     assert fmt != 2 or bias is None or bias.numel() >= n_out
-    r = rope or {}
-    T_max = r["kc"].shape[-2] if rope else 0
-    if rope and is_fp8_cache(r["kc"]):
-        epi |= EPI_KV_FP8
-    base = sbuf.data_ptr()
-    _cmax_set(lib, cmax, epi)
-    args = [int(fmt), _p(wq), base, base + sc_bytes, (base + sc_bytes + dd_bytes) if gain else None, _p(x),
-            x.stride(0), K, n, M, _p(out), out.stride(0), _p(bias), int(bool(norm)), eps, _p(r.get("slot")),
-            _p(r.get("pos")), _p(r.get("cos_t")), _p(r.get("sin_t")), _p(r.get("kc")), _p(r.get("vtc")),
-            r.get("H", 0), r.get("Hkv", 0), r.get("hd", 0), T_max, epi]
-    rc = lib.cain_gemm_q6(*args, int(tile0), _stream()) if fmt == 2 else lib.cain_gemm_q4(*args, _stream())
-    _check(rc, name)
+    g, out = _gemm_record(wq, sbuf, x, n, epi, bias, out, norm, eps, rope, n_out)
+    g.fmt, g.tile0, g.dd = int(fmt), int(tile0), sbuf.data_ptr() + sc_bytes
+    if gain:
+        g.gain = sbuf.data_ptr() + sc_bytes + dd_bytes
+    _cmax_set(lib, cmax, g.epi)
+    _check(lib.cain_gemm_gguf(g, _stream()), name)
     _cmax_check(lib, cmax)
     return out
 
@@ -578,36 +548,30 @@ def w8a8_eligible(n: int, k: int, m: int) -> bool:
     return bool(load().cain_w8a8_eligible(n, k, m))
 
 
+def _gemm_a8(name: str, entry: str, w, sc, x, n: int, epi: int, bias, out, norm: bool, eps: float, rope) -> torch.Tensor:
+    """``gemm_w8a8`` / ``gemm_w4a8`` after their weight checks: the rows quantised, the record on them, the call."""
+    lib = load()
+    M, K = x.shape
+    assert w8a8_eligible(n, K, M), (n, K, M)
+    g, out = _gemm_record(w, sc, x, n, epi, bias, out, False, 0.0, rope)
+    x8, xs = quant_rows(x, norm, eps)
+    g.X, g.ldx, g.xs = x8.data_ptr(), K, xs.data_ptr()
+    g.ws_bytes = int(lib.cain_w8a8_ws_bytes(n, K, M))
+    ws = _workspace(x.device, g.ws_bytes)
+    g.ws = _p(ws)
+    _check(getattr(lib, entry)(g, _stream()), name)
+    return out
+
+
 def gemm_w8a8(wq8: torch.Tensor, scale: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16, bias=None,
               out: Optional[torch.Tensor] = None, norm: bool = False, eps: float = 1e-6, rope=None) -> torch.Tensor:
     """W8A8 wide GEMM (csrc/wgemm8.hip, 16 < M <= 256): the bf16 rows of ``x`` are quantised per row to e4m3
     (``quant_rows``, the RMSNorm folded into the row scale when ``norm``), then y = epi(xs * scale * x8 . q^T)
     with q packed by ``models.weights.pack_mfma_a_fp8_k128``.  Epilogues and ``rope`` as ``gemm_w8``."""
-    lib = load()
     _gpu(wq8, scale, x)
-    M, K = x.shape
+    K = x.shape[1]
     assert wq8.dtype == torch.uint8 and wq8.shape[0] * 16 == n and wq8.shape[1] * 64 == K, (tuple(wq8.shape), K, n)
-    assert w8a8_eligible(n, K, M), (n, K, M)
-    n_out = n // 2 if epi in (EPI_SILU, EPI_GELU) else n
-    if epi == EPI_RESID:
-        assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
-    if out is None:
-        out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
-    x8, xs = quant_rows(x, norm, eps)
-    r = rope or {}
-    if epi == EPI_QKV_ROPE:
-        assert rope is not None, "EPI_QKV_ROPE needs the rope/cache arguments"
-        if is_fp8_cache(r["kc"]):
-            epi |= EPI_KV_FP8
-    T_max = r["kc"].shape[-2] if rope else 0
-    nbytes = int(lib.cain_w8a8_ws_bytes(n, K, M))
-    ws = _workspace(x.device, nbytes)
-    rc = lib.cain_gemm_w8a8(_p(wq8), _p(scale), _p(x8), K, _p(xs), K, n, M, _p(out), out.stride(0), _p(bias),
-                            _p(r.get("slot")), _p(r.get("pos")), _p(r.get("cos_t")), _p(r.get("sin_t")),
-                            _p(r.get("kc")), _p(r.get("vtc")), r.get("H", 0), r.get("Hkv", 0), r.get("hd", 0), T_max,
-                            _p(ws), nbytes, epi, _stream())
-    _check(rc, "gemm_w8a8")
-    return out
+    return _gemm_a8("gemm_w8a8", "cain_gemm_fp8a8", wq8, scale, x, n, epi, bias, out, norm, eps, rope)
 
 
 def gemm_w4a8(wq: torch.Tensor, wsc: torch.Tensor, x: torch.Tensor, n: int, epi: int = EPI_BF16, bias=None,
@@ -616,32 +580,11 @@ def gemm_w4a8(wq: torch.Tensor, wsc: torch.Tensor, x: torch.Tensor, n: int, epi:
     (``models.weights.pack_mxfp4``: wq uint8 [N/16, K/128, 64, 16], wsc e8m0 bytes [N/16, K/128, 64]) on the
     block-scaled f8f6f4 MFMA against the per-row e4m3 quantisation of ``x`` (``quant_rows``); y = epi(xs * x8 . W^T).
     Epilogues and ``rope`` as ``gemm_w8a8``."""
-    lib = load()
     _gpu(wq, wsc, x)
-    M, K = x.shape
+    K = x.shape[1]
     assert wq.dtype == torch.uint8 and tuple(wq.shape) == (n // 16, K // 128, 64, 16), (tuple(wq.shape), K, n)
     assert wsc.dtype == torch.uint8 and wsc.numel() * 32 == n * K, (tuple(wsc.shape), K, n)
-    assert w8a8_eligible(n, K, M), (n, K, M)
-    n_out = n // 2 if epi in (EPI_SILU, EPI_GELU) else n
-    if epi == EPI_RESID:
-        assert out is not None and out.shape == (M, n_out), "EPI_RESID updates `out` (the residual) in place"
-    if out is None:
-        out = torch.empty(M, n_out, device=x.device, dtype=torch.float32 if epi == EPI_F32 else torch.bfloat16)
-    x8, xs = quant_rows(x, norm, eps)
-    r = rope or {}
-    if epi == EPI_QKV_ROPE:
-        assert rope is not None, "EPI_QKV_ROPE needs the rope/cache arguments"
-        if is_fp8_cache(r["kc"]):
-            epi |= EPI_KV_FP8
-    T_max = r["kc"].shape[-2] if rope else 0
-    nbytes = int(lib.cain_w8a8_ws_bytes(n, K, M))
-    ws = _workspace(x.device, nbytes)
-    rc = lib.cain_gemm_w4a8(_p(wq), _p(wsc), _p(x8), K, _p(xs), K, n, M, _p(out), out.stride(0), _p(bias),
-                            _p(r.get("slot")), _p(r.get("pos")), _p(r.get("cos_t")), _p(r.get("sin_t")),
-                            _p(r.get("kc")), _p(r.get("vtc")), r.get("H", 0), r.get("Hkv", 0), r.get("hd", 0), T_max,
-                            _p(ws), nbytes, epi, _stream())
-    _check(rc, "gemm_w4a8")
-    return out
+    return _gemm_a8("gemm_w4a8", "cain_gemm_mxfp4a8", wq, wsc, x, n, epi, bias, out, norm, eps, rope)
 
 
 def set_w4a8_min_rows(m: int) -> None:

@@ -1,0 +1,115 @@
+// The C API of libcain_kernels.so that crosses a file boundary: every entry point one .hip file defines and another
+// calls, declared once (host-only declarations; common.h includes this header, so each definition is checked against
+// its prototype), and CainGemm, the one call record of every GEMM entry (ops/__init__.py mirrors it in ctypes).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "spec.h"
+
+#define CAIN_API extern "C" __attribute__((visibility("default")))
+
+extern "C" {
+
+// One GEMM call: Y = epi(B(X)[M, K] . W[N, K]^T).  Every family reads X, ldx, K, N, M, Y, ldy, bias, W, epi and, under
+// EPI_QKV_ROPE, slot .. T_max; fields a family does not read are zero.  What else each entry reads:
+//   cain_gemm_bf16     norm, eps; waves; ws / ws_bytes (cain_gemm_ws_bytes, zeroed once; null: the skinny kernel)
+//   cain_gemm_fp8      norm, eps; sc: fp32 scale per weight row
+//   cain_gemm_mxfp4    norm, eps; sc: e8m0 scale bytes; ws / ws_bytes (cain_gemm_w4_ws_bytes; null: never split)
+//   cain_gemm_gguf     norm, eps; fmt; sc, dd: the format's scale arrays (dd null for Q4_0); gain; tile0 (Q6_K only)
+//   cain_gemm_fp8a8    X / ldx: the e4m3 rows of cain_quant_rows, xs their scales; sc as fp8; ws / ws_bytes
+//   cain_gemm_mxfp4a8  the same with sc as mxfp4 (ws: cain_w8a8_ws_bytes for both)
+struct CainGemm {
+  const void* W;      // packed weights, in the family's packing
+  const void* sc;     // weight scales (null: bf16)
+  const void* dd;     // GGUF Q4_K (d, dmin) / Q6_K fp32 super-block scales
+  const float* gain;  // GGUF: fp32 RMSNorm gain applied to the activations (null: none, or folded into W)
+  const float* xs;    // A8: per-row activation scales
+  const void* X;
+  void* Y;
+  const float* bias;
+  // EPI_QKV_ROPE
+  const int* slot;
+  const int* pos;
+  const float* cos_t;
+  const float* sin_t;
+  void* kc;
+  void* vtc;
+  void* ws;
+  long long ws_bytes;
+  int ldx, K, N, M, ldy;
+  int norm;  // fused RMSNorm of the rows of X
+  float eps;
+  int H, Hkv, hd, T_max;
+  int epi;    // EPI_* (gemm_epi.h), EPI_KV_FP8 or-ed in
+  int fmt;    // GGUF: 0 Q4_0, 1 Q4_K, 2 Q6_K (gemm_q.h)
+  int tile0;  // GGUF Q6_K: the 16-row tile of the whole projection the first of the N weight rows is
+  int waves;  // bf16 skinny kernel: waves per workgroup (0: the rule)
+};
+
+}  // extern "C"
+
+// ---- GEMMs (gemm.hip, gemm_w8.hip, gemm_w4.hip, gemm_qstream.hip, wgemm8.hip, wgemm.hip)
+CAIN_API int cain_gemm_size();
+CAIN_API int cain_gemm_bf16(const CainGemm* g, hipStream_t st);
+CAIN_API int cain_gemm_fp8(const CainGemm* g, hipStream_t st);
+CAIN_API int cain_gemm_mxfp4(const CainGemm* g, hipStream_t st);
+CAIN_API int cain_gemm_gguf(const CainGemm* g, hipStream_t st);
+CAIN_API int cain_gemm_fp8a8(const CainGemm* g, hipStream_t st);
+CAIN_API int cain_gemm_mxfp4a8(const CainGemm* g, hipStream_t st);
+CAIN_API int cain_gemm_q4_rows(int K, int epi);
+CAIN_API int cain_gemm_q6_rows(int K, int epi);
+CAIN_API int cain_quant_rows(const void* x, int ldx, int K, int M, void* x8, int ld8, float* xs, int norm, float eps,
+                             hipStream_t st);
+CAIN_API int cain_w8a8_eligible(int N, int K, int M);
+CAIN_API int cain_wgemm_eligible(int N, int K, int M);
+CAIN_API long long cain_wgemm_ws_bytes(int N, int K, int M);
+CAIN_API int cain_wgemm_plan(int N, int K, int M);
+// Chunk maxima of the next few-row fp32-logits GEMM (gemm.hip): set by the caller, claimed by the entry that runs
+// it for its GemmArgs::cmax (null: none pending or N not whole chunks), reported written by cain_gemm_cmax_take()
+CAIN_API void cain_gemm_set_cmax(float* cmax);
+CAIN_API int cain_gemm_cmax_take();
+CAIN_API float* cain_gemm_cmax_claim(int N);
+
+// CUs the launch sizing of the persistent / CU-proportional grids assumes: the device's, or the smaller budget of
+// cain_set_cu_budget (runtime.hip) while the work runs on a CU-masked stream (cain_stream_create_cu_limited).
+CAIN_API int cain_cu_budget();
+
+// ---- the rest of a forward (norm.hip, attention.hip, sample.hip, logprob.hip, spec.hip)
+CAIN_API int cain_embed(const int* tok, const void* E, void* out, int ldo, int M, int d, float scale, hipStream_t st);
+CAIN_API int cain_attention_ex(const void* q, const void* kc, const void* vtc, const int* slot, const int* pos,
+                               float* part_o, float* part_ml, unsigned* counters, void* out, int ldo, int M, int H,
+                               int Hkv, int hd, int T_max, int nsplit, float scale, int kv8, float kscale,
+                               float vscale, hipStream_t st);
+CAIN_API int cain_attention(const void* q, const void* kc, const void* vtc, const int* slot, const int* pos,
+                            float* part_o, float* part_ml, unsigned* counters, void* out, int ldo, int M, int H,
+                            int Hkv, int hd, int T_max, int nsplit, float scale, hipStream_t st);
+CAIN_API int cain_sample(float* logits, int ldl, int V, int* tok, int* pos, int* gen, int ldg, int* n_gen,
+                         const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
+                         const void* params, hipStream_t st);
+CAIN_API long long cain_sample_ws_bytes(int M);
+CAIN_API int cain_sample_split_max();
+CAIN_API int cain_sample_cm_enabled();
+CAIN_API int cain_sample_cm(float* logits, int ldl, int V, const float* cmax, int* tok, int* pos, int* gen, int ldg,
+                            int* n_gen, const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
+                            const void* params, hipStream_t st);
+CAIN_API int cain_sample_lean(float* logits, int ldl, int V, const float* cmax, int* tok, int* pos, int* gen, int ldg,
+                              int* n_gen, const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
+                              const void* params, hipStream_t st);
+CAIN_API int cain_sample_ex(float* logits, int ldl, int V, int* tok, int* pos, int* gen, int ldg, int* n_gen,
+                            const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
+                            const void* params, void* ws, long long ws_bytes, hipStream_t st);
+CAIN_API int cain_logprob_rows(const float* logits, int ldl, int V, int M, const int* slot, const int* done,
+                               const int* topn, int nmax, const int* target, float* lse, float* lp, int* top_id,
+                               float* top_lp, hipStream_t st);
+CAIN_API int cain_logprob_pre(const float* logits, int ldl, int V, int M, const int* slot, const int* done,
+                              const int* topn, int nmax, const int* n_gen, const int* hist, int ldg, int* top_id,
+                              float* top_lp, void* keep, hipStream_t st);
+CAIN_API int cain_logprob_chosen(const float* logits, int ldl, int V, int M, const int* gen, int ldg, const void* keep,
+                                 float* lp, hipStream_t st);
+CAIN_API int cain_spec_draft(const CainSpec* s, int R, int T_max, const int* tok, const int* pos, const int* slot,
+                             const int* n_gen, const int* max_new, const int* done, const int* hist,
+                             const void* params, hipStream_t st);
+CAIN_API int cain_spec_accept(const CainSpec* s, int R, int T_max, int* tok, int* pos, const int* slot, int* n_gen,
+                              const int* max_new, int* done, int* hist, int* gen, int ldg, const void* params,
+                              hipStream_t st);

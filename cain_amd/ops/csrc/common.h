@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cain_api.h"
+
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -11,12 +13,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
 typedef uint16_t u16x4 __attribute__((ext_vector_type(4)));
-
-#define CAIN_API extern "C" __attribute__((visibility("default")))
-
-// CUs the launch sizing of the persistent / CU-proportional grids assumes: the device's, or the smaller budget of
-// cain_set_cu_budget (runtime.hip) while the work runs on a CU-masked stream (cain_stream_create_cu_limited).
-extern "C" int cain_cu_budget();
 
 __device__ __forceinline__ float bf2f(__bf16 v) { return static_cast<float>(v); }
 __device__ __forceinline__ __bf16 f2bf(float v) { return static_cast<__bf16>(v); }  // v_cvt_pk_bf16_f32 (RNE, NaN-safe)

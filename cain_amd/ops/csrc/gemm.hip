@@ -1003,11 +1003,6 @@ static bool bgemm_eligible(int N, int K, int M) {
   return M > bgemm_min_m() && M <= 256 && K % (32 * BG_CK) == 0 && (M > 32 || N >= 8192 || K > 4096);
 }
 
-// wgemm.hip: the wide-batch (64 < M <= 256) kernel; its split-K slabs live after the batched path's counters
-CAIN_API int cain_wgemm_eligible(int N, int K, int M);
-CAIN_API long long cain_wgemm_ws_bytes(int N, int K, int M);
-int wgemm_dispatch(const GemmArgs& a, int epi, bool norm, void* ws, long long ws_bytes, hipStream_t st);
-
 // Skinny split-K slabs: [tiles][ks][64] f32x4 partials + [tiles][ks][16] row sums of squares, after the counters
 static size_t skinny_split_ws_bytes(int N, int ks) {
   return GEMM_SLAB_OFFSET + (size_t)(N / 16) * ks * (256 + 16) * sizeof(float);
@@ -1027,7 +1022,6 @@ CAIN_API long long cain_gemm_ws_bytes(int N, int K, int M) {
 // that call, consumed (and cleared) by it when it runs on the plain skinny kernel; cain_gemm_cmax_take() then
 // reports that the buffer was written, so the runtime can hand it to the chunk-max sampler.
 // (thread-local: engines of different models may run forwards on different threads of one process)
-CAIN_API int cain_wgemm_plan(int N, int K, int M);
 static thread_local float* g_next_cmax = nullptr;
 static thread_local int g_cmax_used = 0;
 CAIN_API void cain_gemm_set_cmax(float* cmax) { g_next_cmax = cmax, g_cmax_used = 0; }
@@ -1045,51 +1039,24 @@ CAIN_API float* cain_gemm_cmax_claim(int N) {
   return p;
 }
 
-// Entry used by the runtime and the bindings.  norm != 0 selects the fused RMSNorm (gain pre-folded into Wp).
-CAIN_API int cain_skinny_gemm_ex(const void* Wp, const void* X, int ldx, int K, int N, int M, void* Y, int ldy,
-                                 const float* bias, int norm, float eps, const int* slot, const int* pos,
-                                 const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                                 int T_max, int epi, int waves, hipStream_t st) {
-  const int kv8 = (epi & EPI_KV_FP8) ? 1 : 0;
-  epi &= EPI_MASK;
-  GemmArgs a{};
-  a.Wp = reinterpret_cast<const bf16x8*>(Wp);
-  a.X = reinterpret_cast<const __bf16*>(X);
-  a.ldx = ldx, a.K = K, a.N = N, a.M = M, a.Y = Y, a.ldy = ldy, a.bias = bias;
-  a.eps = eps;
-  a.slot = slot, a.pos = pos, a.cos_t = cos_t, a.sin_t = sin_t;
-  a.kc = reinterpret_cast<__bf16*>(kc), a.vtc = reinterpret_cast<__bf16*>(vtc);
-  a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = kv8;
-  if (epi == EPI_QKV_ROPE && (hd % 16 || (hd / 2) % 8)) return -1;
-  if (epi == EPI_F32 && g_next_cmax && M <= 16 && N % 16 == 0) {
-    a.cmax = g_next_cmax, a.ld_cm = N / 16;
-    g_next_cmax = nullptr, g_cmax_used = 1;
-  }
-  return gemm_dispatch(a, epi, norm != 0, waves, st);
-}
+CAIN_API int cain_gemm_size() { return int(sizeof(CainGemm)); }
 
-// Full entry: the wide kernel (wgemm.hip) for 64 < M <= 256, the batched path for 16 < M <= 64, when a
-// workspace of cain_gemm_ws_bytes() (zeroed once) is given; the skinny kernel otherwise.
-CAIN_API int cain_gemm(const void* Wp, const void* X, int ldx, int K, int N, int M, void* Y, int ldy,
-                       const float* bias, int norm, float eps, const int* slot, const int* pos,
-                       const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd, int T_max,
-                       void* ws, long long ws_bytes, int epi_flags, int waves, hipStream_t st) {
-  const int epi = epi_flags & EPI_MASK, kv8 = (epi_flags & EPI_KV_FP8) ? 1 : 0;
+// The bf16 entry of the runtime and the bindings; g->norm selects the fused RMSNorm (gain pre-folded into W).  The
+// wide kernel (wgemm.hip; its split-K slabs live after the batched path's counters) for 64 < M <= 256, the batched
+// path for 16 < M <= 64, when a workspace of cain_gemm_ws_bytes() (zeroed once) is given; the skinny kernel otherwise.
+CAIN_API int cain_gemm_bf16(const CainGemm* g, hipStream_t st) {
+  const int K = g->K, N = g->N, M = g->M, epi = g->epi & EPI_MASK;
+  void* const ws = g->ws;
+  const long long ws_bytes = g->ws_bytes;
+  GemmArgs a;
+  if (!gemm_args(*g, a)) return -1;
   if (ws && cain_wgemm_eligible(N, K, M) && ws_bytes >= (long long)BG_COUNTER_BYTES) {
-    if (epi == EPI_QKV_ROPE && (hd % 16 || (hd / 2) % 8)) return -1;
-    GemmArgs a{};
-    a.Wp = reinterpret_cast<const bf16x8*>(Wp);
-    a.X = reinterpret_cast<const __bf16*>(X);
-    a.ldx = ldx, a.K = K, a.N = N, a.M = M, a.Y = Y, a.ldy = ldy, a.bias = bias;
-    a.eps = eps;
-    a.slot = slot, a.pos = pos, a.cos_t = cos_t, a.sin_t = sin_t;
-    a.kc = reinterpret_cast<__bf16*>(kc), a.vtc = reinterpret_cast<__bf16*>(vtc);
-    a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = kv8;
     // the wide LM head writes the chunk maxima in its unsplit epilogue (the plan's split count is 1 there)
     const bool cm = epi == EPI_F32 && g_next_cmax && N % 16 == 0 && cain_wgemm_plan(N, K, M) / 64 == 1;
-    if (cm) a.cmax = g_next_cmax, a.ld_cm = N / 16;
+    GemmArgs w = a;
+    if (cm) w.cmax = g_next_cmax, w.ld_cm = N / 16;
     // the batched path's counters (first BG_COUNTER_BYTES) must stay zero: the slabs go after them
-    const int rc = wgemm_dispatch(a, epi, norm != 0, static_cast<char*>(ws) + BG_COUNTER_BYTES,
+    const int rc = wgemm_dispatch(w, epi, g->norm != 0, static_cast<char*>(ws) + BG_COUNTER_BYTES,
                                   ws_bytes - (long long)BG_COUNTER_BYTES, st);
     if (rc >= 0) {
       if (cm) g_next_cmax = nullptr, g_cmax_used = 1;
@@ -1098,40 +1065,24 @@ CAIN_API int cain_gemm(const void* Wp, const void* X, int ldx, int K, int N, int
   }
   if (ws && bgemm_eligible(N, K, M) && K % 32 == 0 && N % 16 == 0) {
     const BgPlan p = bgemm_plan(N, K, M, bgemm_ntw());
-    if ((long long)bgemm_ws_bytes(p) <= ws_bytes && p.nblk * 4 <= (int)BG_COUNTER_BYTES) {
-      GemmArgs a{};
-      a.Wp = reinterpret_cast<const bf16x8*>(Wp);
-      a.X = reinterpret_cast<const __bf16*>(X);
-      a.ldx = ldx, a.K = K, a.N = N, a.M = M, a.Y = Y, a.ldy = ldy, a.bias = bias;
-      a.eps = eps;
-      a.slot = slot, a.pos = pos, a.cos_t = cos_t, a.sin_t = sin_t;
-      a.kc = reinterpret_cast<__bf16*>(kc), a.vtc = reinterpret_cast<__bf16*>(vtc);
-      a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = kv8;
-      if (epi == EPI_QKV_ROPE && (hd % 16 || (hd / 2) % 8)) return -1;
-      return bgemm_dispatch(a, epi, norm != 0, p, ws, st);
-    }
+    if ((long long)bgemm_ws_bytes(p) <= ws_bytes && p.nblk * 4 <= (int)BG_COUNTER_BYTES)
+      return bgemm_dispatch(a, epi, g->norm != 0, p, ws, st);
   }
   if (ws && M <= 16 && K % 32 == 0 && N % 16 == 0) {
     const int ks = skinny_split(N, K, M);
     if (ks > 1 && (long long)skinny_split_ws_bytes(N, ks) <= ws_bytes && (N / 16) * 4 <= (int)BG_COUNTER_BYTES) {
-      if (epi == EPI_QKV_ROPE && (hd % 16 || (hd / 2) % 8)) return -1;
-      GemmArgs a{};
-      a.Wp = reinterpret_cast<const bf16x8*>(Wp);
-      a.X = reinterpret_cast<const __bf16*>(X);
-      a.ldx = ldx, a.K = K, a.N = N, a.M = M, a.Y = Y, a.ldy = ldy, a.bias = bias;
-      a.eps = eps;
-      a.slot = slot, a.pos = pos, a.cos_t = cos_t, a.sin_t = sin_t;
-      a.kc = reinterpret_cast<__bf16*>(kc), a.vtc = reinterpret_cast<__bf16*>(vtc);
-      a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = kv8;
       SkArgs sk{};
       sk.ks = ks;
       sk.counters = reinterpret_cast<unsigned*>(ws);  // the batched path's tickets (both reset their own)
       sk.part = reinterpret_cast<float*>(static_cast<char*>(ws) + GEMM_SLAB_OFFSET);
       sk.part_ss = sk.part + (size_t)(N / 16) * ks * 256;
-      return gemm_dispatch(a, epi, norm != 0, waves, st, &sk);
+      return gemm_dispatch(a, epi, g->norm != 0, g->waves, st, &sk);
     }
   }
-  return cain_skinny_gemm_ex(Wp, X, ldx, K, N, M, Y, ldy, bias, norm, eps, slot, pos, cos_t, sin_t, kc, vtc, H, Hkv,
-                             hd, T_max, epi_flags, waves, st);
+  // the plain skinny kernel: any shape the paths above did not take
+  if (epi == EPI_F32 && g_next_cmax && M <= 16 && N % 16 == 0) {
+    a.cmax = g_next_cmax, a.ld_cm = N / 16;
+    g_next_cmax = nullptr, g_cmax_used = 1;
+  }
+  return gemm_dispatch(a, epi, g->norm != 0, g->waves, st);
 }
-

@@ -211,6 +211,19 @@ __device__ __forceinline__ void epi_cmax(const GemmArgs& a, int gt, int m, int l
   if ((lane >> 4) == 0 && m < a.M) a.cmax[(size_t)m * a.ld_cm + gt] = mx;
 }
 
-// Host side (gemm.hip): the cmax buffer pending for the next few-row fp32-logits GEMM of N columns, now marked
-// written (null: none pending or N not whole chunks) -- every weight-format entry claims it for its GemmArgs::cmax
-CAIN_API float* cain_gemm_cmax_claim(int N);
+// Host side, every GEMM entry: the GemmArgs of a call record (cain_api.h; msplit and cmax are the caller's).  False:
+// refused -- the fused QKV epilogue needs head sizes of whole 16-row tiles whose halves are whole 8-pair groups.
+static inline bool gemm_args(const CainGemm& g, GemmArgs& a) {
+  a = GemmArgs{};
+  a.Wp = reinterpret_cast<const bf16x8*>(g.W);
+  a.X = reinterpret_cast<const __bf16*>(g.X);
+  a.ldx = g.ldx, a.K = g.K, a.N = g.N, a.M = g.M, a.Y = g.Y, a.ldy = g.ldy, a.bias = g.bias;
+  a.eps = g.eps;
+  a.slot = g.slot, a.pos = g.pos, a.cos_t = g.cos_t, a.sin_t = g.sin_t;
+  a.kc = reinterpret_cast<__bf16*>(g.kc), a.vtc = reinterpret_cast<__bf16*>(g.vtc);
+  a.H = g.H, a.Hkv = g.Hkv, a.hd = g.hd, a.T_max = g.T_max, a.kv8 = (g.epi & EPI_KV_FP8) ? 1 : 0;
+  return !((g.epi & EPI_MASK) == EPI_QKV_ROPE && (g.hd % 16 || (g.hd / 2) % 8));
+}
+
+// wgemm.hip: the wide-batch (64 < M <= 256) bf16 kernel; ws: >= cain_wgemm_ws_bytes of scratch.  < 0: not taken.
+int wgemm_dispatch(const GemmArgs& a, int epi, bool norm, void* ws, long long ws_bytes, hipStream_t st);

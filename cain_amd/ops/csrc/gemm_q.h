@@ -55,7 +55,7 @@ __device__ __forceinline__ float q6_pair_sum(float v) {
   return v + __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
 }
 
-// ---- the many-row path (gemm_qtile.hip), called by cain_gemm_q4 / cain_gemm_q6 when q_tile_selected()
+// ---- the many-row path (gemm_qtile.hip), called by cain_gemm_gguf when q_tile_selected()
 struct GemmArgs;
 // whether M rows of a (fmt, K, epi) GEMM run on the tile kernels under the current mode (cain_gemm_q_set_tile);
 // `stream_rows`: the stream kernel's rows per launch at (K, epi), > 0

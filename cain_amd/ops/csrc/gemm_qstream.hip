@@ -393,19 +393,23 @@ static int q_stream_rows(int fmt, int K, int epi) {
   return 0;
 }
 
-// One GGUF GEMM: the few-row stream kernels above, or -- more rows than their LDS copy holds (q_stream_rows), where
-// q_tile_selected() -- the tile kernels of gemm_qtile.hip, 64 rows per launch, one pass over the weights each
-// (cain_gemm_q_set_tile(0): as several stream launches).  `tile0`: the global 16-row tile the first of the N rows is
-// in the epilogue's eyes (output columns, bias, QKV head / V row); the weights and scales are addressed from tile 0
-// of their own buffers.  A shape or (format, epilogue) pair without a kernel is refused (-1) before any launch.
-static int q_gemm_run(int fmt, const void* Wq, const void* sc, const void* dd, const float* gain, const void* X,
-                      int ldx, int K, int N, int M, void* Y, int ldy, const float* bias, int norm, float eps,
-                      const int* slot, const int* pos, const float* cos_t, const float* sin_t, void* kc, void* vtc,
-                      int H, int Hkv, int hd, int T_max, int epi_flags, int tile0, hipStream_t st) {
-  const int epi = epi_flags & EPI_MASK;
+// One GGUF GEMM (g->fmt: Q4_0, Q4_K or Q6_K; sc / dd: the format's scale arrays; gain: the RMSNorm gain to apply to the
+// activations, null: none): the few-row stream kernels above, or -- more rows than their LDS copy holds
+// (q_stream_rows), where q_tile_selected() -- the tile kernels of gemm_qtile.hip, 64 rows per launch, one pass over the
+// weights each (cain_gemm_q_set_tile(0): as several stream launches).  `tile0` (Q6_K only): the global 16-row tile the
+// first of the N rows is in the epilogue's eyes (output columns, bias, QKV head / V row); the weights and scales are
+// addressed from tile 0 of their own buffers.  A shape or (format, epilogue) pair without a kernel is refused (-1)
+// before any launch.
+CAIN_API int cain_gemm_gguf(const CainGemm* g, hipStream_t st) {
+  const int fmt = g->fmt, K = g->K, N = g->N, M = g->M, tile0 = g->tile0, norm = g->norm, epi = g->epi & EPI_MASK;
+  const void *sc = g->sc, *dd = g->dd;
+  const float* gain = g->gain;
+  if (tile0 != 0 && fmt != Q6F_K) return -1;  // first of all: a tile offset is Q6_K's alone
   if (K < 256 || K % 256 || N < 16 || N % 16 || M < 1 || tile0 < 0 || fmt < Q4F_0 || fmt > Q6F_K) return -1;
-  if (!Wq || !sc || (fmt != Q4F_0 && !dd) || !q_stream_instance(fmt, epi)) return -1;
-  if (epi == EPI_QKV_ROPE && (hd % 16 || (hd / 2) % 8)) return -1;
+  if (!g->W || !sc || (fmt != Q4F_0 && !dd) || !q_stream_instance(fmt, epi)) return -1;
+  GemmArgs all;
+  if (!gemm_args(*g, all)) return -1;
+  all.msplit = 1;
   const int rows = q_stream_rows(fmt, K, epi);
   if (rows == 0) return -1;
   const bool tile = q_tile_selected(fmt, K, M, epi, rows);
@@ -415,17 +419,12 @@ static int q_gemm_run(int fmt, const void* Wq, const void* sc, const void* dd, c
   float* cm = (epi == EPI_F32 && tile0 == 0) ? cain_gemm_cmax_claim(N) : nullptr;
   for (int m0 = 0; m0 < M; m0 += per) {
     const int mc = std::min(per, M - m0);
-    GemmArgs a{};
-    a.Wp = reinterpret_cast<const bf16x8*>(Wq);
-    a.X = reinterpret_cast<const __bf16*>(X) + (size_t)m0 * ldx;
-    a.ldx = ldx, a.K = K, a.N = N, a.M = mc, a.ldy = ldy, a.bias = bias;
-    const size_t ybytes = epi == EPI_F32 ? 4 : 2;
-    a.Y = static_cast<char*>(Y) + (size_t)m0 * ldy * ybytes;
-    a.eps = eps;
-    a.slot = slot ? slot + m0 : nullptr, a.pos = pos ? pos + m0 : nullptr, a.cos_t = cos_t, a.sin_t = sin_t;
-    a.kc = reinterpret_cast<__bf16*>(kc), a.vtc = reinterpret_cast<__bf16*>(vtc);
-    a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = (epi_flags & EPI_KV_FP8) ? 1 : 0;
-    a.msplit = 1;
+    GemmArgs a = all;  // rows m0 .. m0 + mc
+    a.X += (size_t)m0 * a.ldx;
+    a.M = mc;
+    a.Y = static_cast<char*>(a.Y) + (size_t)m0 * a.ldy * (epi == EPI_F32 ? 4 : 2);
+    if (a.slot) a.slot += m0;
+    if (a.pos) a.pos += m0;
     if (cm) a.cmax = cm + (size_t)m0 * (N / 16), a.ld_cm = N / 16;
     if (tile) {
       const hipError_t e = q_tile_launch(fmt, a, sc, dd, gain, epi, norm != 0, tile0, st);
@@ -447,24 +446,3 @@ static int q_gemm_run(int fmt, const void* Wq, const void* sc, const void* dd, c
 
 CAIN_API int cain_gemm_q4_rows(int K, int epi) { return q_stream_rows(Q4F_0, K, epi & EPI_MASK); }  // Q4_K: the same
 CAIN_API int cain_gemm_q6_rows(int K, int epi) { return q_stream_rows(Q6F_K, K, epi & EPI_MASK); }
-
-// Same GEMM arguments as cain_gemm_w4 (gemm_w4.hip) plus the format (0 Q4_0, 1 Q4_K), its scale arrays and the
-// RMSNorm gain to apply to the activations (null: none).
-CAIN_API int cain_gemm_q4(int fmt, const void* Wq, const void* sc, const void* dd, const float* gain, const void* X,
-                          int ldx, int K, int N, int M, void* Y, int ldy, const float* bias, int norm, float eps,
-                          const int* slot, const int* pos, const float* cos_t, const float* sin_t, void* kc,
-                          void* vtc, int H, int Hkv, int hd, int T_max, int epi_flags, hipStream_t st) {
-  if (fmt != Q4F_0 && fmt != Q4F_K) return -1;
-  return q_gemm_run(fmt, Wq, sc, dd, gain, X, ldx, K, N, M, Y, ldy, bias, norm, eps, slot, pos, cos_t, sin_t, kc, vtc,
-                    H, Hkv, hd, T_max, epi_flags, 0, st);
-}
-
-// cain_gemm_q4's arguments (fmt: 2, Q6_K; sc: the int8 group scales, dd: the fp32 super-block scales) plus `tile0`.
-CAIN_API int cain_gemm_q6(int fmt, const void* Wq, const void* sc, const void* dd, const float* gain, const void* X,
-                          int ldx, int K, int N, int M, void* Y, int ldy, const float* bias, int norm, float eps,
-                          const int* slot, const int* pos, const float* cos_t, const float* sin_t, void* kc,
-                          void* vtc, int H, int Hkv, int hd, int T_max, int epi_flags, int tile0, hipStream_t st) {
-  if (fmt != Q6F_K) return -1;
-  return q_gemm_run(fmt, Wq, sc, dd, gain, X, ldx, K, N, M, Y, ldy, bias, norm, eps, slot, pos, cos_t, sin_t, kc, vtc,
-                    H, Hkv, hd, T_max, epi_flags, tile0, st);
-}

@@ -373,11 +373,8 @@ bool q_tile_selected(int fmt, int K, int M, int epi, int stream_rows) {
   return q_tile_rule(fmt, K, M, epi, stream_rows);
 }
 
-CAIN_API int cain_gemm_q4_rows(int K, int epi);
-CAIN_API int cain_gemm_q6_rows(int K, int epi);
-
-// How many times cain_gemm_q4 (fmt 0, 1) / cain_gemm_q6 (fmt 2) stream the weight matrix for M rows under the
-// current mode; -1 where the entry refuses the shape.
+// How many times cain_gemm_gguf streams the weight matrix for M rows under the current mode; -1 where the entry
+// refuses the shape.
 CAIN_API int cain_gemm_q_passes(int fmt, int K, int M, int epi) {
   epi &= EPI_MASK;
   if (fmt < Q4F_0 || fmt > Q6F_K || K < 256 || K % 256 || M < 1) return -1;

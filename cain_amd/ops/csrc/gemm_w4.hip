@@ -526,37 +526,14 @@ CAIN_API long long cain_gemm_w4_ws_bytes(int N, int K, int M) {
   return N % 16 ? 0 : w4_split_bytes(N, 4);
 }
 
-CAIN_API int cain_gemm_w4_ex(const void* Wp, const void* wsc, const void* X, int ldx, int K, int N, int M, void* Y,
-                             int ldy, const float* bias, int norm, float eps, const int* slot, const int* pos,
-                             const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                             int T_max, void* ws, long long ws_bytes, int epi_flags, hipStream_t st);
-
-// Same arguments as cain_gemm_w8 (gemm_w8.hip); Wp is the MXFP4 packing, wsc its e8m0 scale bytes.  No workspace:
-// never split (cain_gemm_w4_ex is the engine's entry).
-CAIN_API int cain_gemm_w4(const void* Wp, const void* wsc, const void* X, int ldx, int K, int N, int M, void* Y, int ldy,
-                          const float* bias, int norm, float eps, const int* slot, const int* pos, const float* cos_t,
-                          const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd, int T_max, int epi_flags,
-                          hipStream_t st) {
-  return cain_gemm_w4_ex(Wp, wsc, X, ldx, K, N, M, Y, ldy, bias, norm, eps, slot, pos, cos_t, sin_t, kc, vtc, H, Hkv,
-                         hd, T_max, nullptr, 0, epi_flags, st);
-}
-
-// ws: zeroed at allocation; its first W4_CTR_BYTES are tickets that every split launch leaves zero
-CAIN_API int cain_gemm_w4_ex(const void* Wp, const void* wsc, const void* X, int ldx, int K, int N, int M, void* Y,
-                             int ldy, const float* bias, int norm, float eps, const int* slot, const int* pos,
-                             const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                             int T_max, void* ws, long long ws_bytes, int epi_flags, hipStream_t st) {
-  const int epi = epi_flags & EPI_MASK;
+// The call record of cain_gemm_fp8 (gemm_w8.hip) with W in the MXFP4 packing and sc its e8m0 scale bytes.
+// ws: zeroed at allocation; its first W4_CTR_BYTES are tickets that every split launch leaves zero (null: never split)
+CAIN_API int cain_gemm_mxfp4(const CainGemm* g, hipStream_t st) {
+  const int K = g->K, N = g->N, M = g->M, norm = g->norm, epi = g->epi & EPI_MASK;
+  void* const ws = g->ws;
   if (K % 128 || N % 16 || M < 1 || M > 64) return -1;
-  if (epi == EPI_QKV_ROPE && (hd % 16 || (hd / 2) % 8)) return -1;
-  GemmArgs a{};
-  a.Wp = reinterpret_cast<const bf16x8*>(Wp);
-  a.X = reinterpret_cast<const __bf16*>(X);
-  a.ldx = ldx, a.K = K, a.N = N, a.M = M, a.Y = Y, a.ldy = ldy, a.bias = bias;
-  a.eps = eps;
-  a.slot = slot, a.pos = pos, a.cos_t = cos_t, a.sin_t = sin_t;
-  a.kc = reinterpret_cast<__bf16*>(kc), a.vtc = reinterpret_cast<__bf16*>(vtc);
-  a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = (epi_flags & EPI_KV_FP8) ? 1 : 0;
+  GemmArgs a;
+  if (!gemm_args(*g, a)) return -1;
   const int n_cu = w4_n_cu();
   const int var = w4_variant(N, K, M, epi, n_cu);
   const int nb = W4_NB[var], waves = W4_WAVES[var];
@@ -569,7 +546,7 @@ CAIN_API int cain_gemm_w4_ex(const void* Wp, const void* wsc, const void* X, int
   int np = npairs;
   if (w4_is_stream(var)) {  // persistent: at most the resident workgroups (2 of 8 waves / 4 of 4 waves per CU)
     a.msplit = 1;
-    sp.ks = ws ? w4_split(var, N, K, epi, n_cu, ws_bytes) : 1;
+    sp.ks = ws ? w4_split(var, N, K, epi, n_cu, g->ws_bytes) : 1;
     if (sp.ks > 1) {
       sp.ctr = static_cast<unsigned*>(ws);
       sp.part = reinterpret_cast<float*>(static_cast<char*>(ws) + W4_PART_OFFSET);
@@ -577,7 +554,7 @@ CAIN_API int cain_gemm_w4_ex(const void* Wp, const void* wsc, const void* X, int
     }
     grid = std::min(np, n_cu * (g_w4_wgs_per_cu ? g_w4_wgs_per_cu : (waves == 8 ? 2 : 4)));
   }
-  const uint8_t* sc = reinterpret_cast<const uint8_t*>(wsc);
+  const uint8_t* sc = static_cast<const uint8_t*>(g->sc);
   const hipError_t e = norm ? w4_launch<true>(epi, var, a, sc, grid, np, sp, st)
                             : w4_launch<false>(epi, var, a, sc, grid, np, sp, st);
   return int(e);

@@ -279,22 +279,13 @@ static hipError_t w8_launch_e(int epi, int var, const GemmArgs& a, const float* 
 #undef CAIN_W8_VAR
 }
 
-// Same arguments as cain_gemm (gemm.hip) plus the per-row weight scales; Wp is the fp8 packing.
-CAIN_API int cain_gemm_w8(const void* Wp, const float* wscale, const void* X, int ldx, int K, int N, int M, void* Y,
-                          int ldy, const float* bias, int norm, float eps, const int* slot, const int* pos,
-                          const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                          int T_max, int epi_flags, hipStream_t st) {
-  const int epi = epi_flags & EPI_MASK;
+// The call record of cain_gemm_bf16 (gemm.hip) with W in the fp8 packing and sc its per-row fp32 scales.
+CAIN_API int cain_gemm_fp8(const CainGemm* g, hipStream_t st) {
+  const int K = g->K, N = g->N, M = g->M, norm = g->norm, epi = g->epi & EPI_MASK;
+  const float* wscale = static_cast<const float*>(g->sc);
   if (K % 64 || N % 16 || M < 1 || M > 64) return -1;
-  if (epi == EPI_QKV_ROPE && (hd % 16 || (hd / 2) % 8)) return -1;
-  GemmArgs a{};
-  a.Wp = reinterpret_cast<const bf16x8*>(Wp);
-  a.X = reinterpret_cast<const __bf16*>(X);
-  a.ldx = ldx, a.K = K, a.N = N, a.M = M, a.Y = Y, a.ldy = ldy, a.bias = bias;
-  a.eps = eps;
-  a.slot = slot, a.pos = pos, a.cos_t = cos_t, a.sin_t = sin_t;
-  a.kc = reinterpret_cast<__bf16*>(kc), a.vtc = reinterpret_cast<__bf16*>(vtc);
-  a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = (epi_flags & EPI_KV_FP8) ? 1 : 0;
+  GemmArgs a;
+  if (!gemm_args(*g, a)) return -1;
   if (epi == EPI_F32)  // the few-row LM head also writes the sampler's chunk maxima
     if (float* cm = cain_gemm_cmax_claim(N)) a.cmax = cm, a.ld_cm = N / 16;
   // (round 2-3's A/B overrides of waves / pairs in flight / tiles / row blocks are fixed at the measured rule)

@@ -21,80 +21,8 @@
 #include <vector>
 
 #include "common.h"
-#include "spec.h"
 
 constexpr int CAIN_MAX_ROWS = 256;  // rows per forward (decode batch / prefill chunk)
-
-CAIN_API int cain_gemm(const void* Wp, const void* X, int ldx, int K, int N, int M, void* Y, int ldy,
-                       const float* bias, int norm, float eps, const int* slot, const int* pos,
-                       const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd, int T_max,
-                       void* ws, long long ws_bytes, int epi, int waves, hipStream_t st);
-CAIN_API int cain_gemm_w8(const void* Wp, const float* wscale, const void* X, int ldx, int K, int N, int M, void* Y,
-                          int ldy, const float* bias, int norm, float eps, const int* slot, const int* pos,
-                          const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                          int T_max, int epi, hipStream_t st);
-CAIN_API int cain_gemm_w4_ex(const void* Wp, const void* wsc, const void* X, int ldx, int K, int N, int M, void* Y,
-                             int ldy, const float* bias, int norm, float eps, const int* slot, const int* pos,
-                             const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                             int T_max, void* ws, long long ws_bytes, int epi_flags, hipStream_t st);
-CAIN_API int cain_gemm_q4(int fmt, const void* Wq, const void* sc, const void* dd, const float* gain, const void* X,
-                          int ldx, int K, int N, int M, void* Y, int ldy, const float* bias, int norm, float eps,
-                          const int* slot, const int* pos, const float* cos_t, const float* sin_t, void* kc,
-                          void* vtc, int H, int Hkv, int hd, int T_max, int epi_flags, hipStream_t st);
-CAIN_API int cain_gemm_q6(int fmt, const void* Wq, const void* sc, const void* dd, const float* gain, const void* X,
-                          int ldx, int K, int N, int M, void* Y, int ldy, const float* bias, int norm, float eps,
-                          const int* slot, const int* pos, const float* cos_t, const float* sin_t, void* kc,
-                          void* vtc, int H, int Hkv, int hd, int T_max, int epi_flags, int tile0, hipStream_t st);
-CAIN_API int cain_gemm_w8a8(const void* Wp8, const float* wscale, const void* X8, int ld8, const float* xs, int K,
-                            int N, int M, void* Y, int ldy, const float* bias, const int* slot, const int* pos,
-                            const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                            int T_max, void* ws, long long ws_bytes, int epi_flags, hipStream_t st);
-CAIN_API int cain_gemm_w4a8(const void* Wq, const void* wsc, const void* X8, int ld8, const float* xs, int K, int N,
-                            int M, void* Y, int ldy, const float* bias, const int* slot, const int* pos,
-                            const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                            int T_max, void* ws, long long ws_bytes, int epi_flags, hipStream_t st);
-CAIN_API int cain_quant_rows(const void* x, int ldx, int K, int M, void* x8, int ld8, float* xs, int norm, float eps,
-                             hipStream_t st);
-CAIN_API int cain_w8a8_eligible(int N, int K, int M);
-CAIN_API int cain_embed(const int* tok, const void* E, void* out, int ldo, int M, int d, float scale, hipStream_t st);
-CAIN_API int cain_attention_ex(const void* q, const void* kc, const void* vtc, const int* slot, const int* pos,
-                               float* part_o, float* part_ml, unsigned* counters, void* out, int ldo, int M, int H,
-                               int Hkv, int hd, int T_max, int nsplit, float scale, int kv8, float kscale,
-                               float vscale, hipStream_t st);
-CAIN_API int cain_attention(const void* q, const void* kc, const void* vtc, const int* slot, const int* pos,
-                            float* part_o, float* part_ml, unsigned* counters, void* out, int ldo, int M, int H,
-                            int Hkv, int hd, int T_max, int nsplit, float scale, hipStream_t st);
-CAIN_API int cain_sample(float* logits, int ldl, int V, int* tok, int* pos, int* gen, int ldg, int* n_gen,
-                         const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                         const void* params, hipStream_t st);
-CAIN_API long long cain_sample_ws_bytes(int M);
-CAIN_API int cain_sample_split_max();
-CAIN_API int cain_sample_cm_enabled();
-CAIN_API int cain_sample_cm(float* logits, int ldl, int V, const float* cmax, int* tok, int* pos, int* gen, int ldg,
-                            int* n_gen, const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                            const void* params, hipStream_t st);
-CAIN_API int cain_sample_lean(float* logits, int ldl, int V, const float* cmax, int* tok, int* pos, int* gen, int ldg,
-                              int* n_gen, const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                              const void* params, hipStream_t st);
-CAIN_API void cain_gemm_set_cmax(float* cmax);
-CAIN_API int cain_gemm_cmax_take();
-CAIN_API int cain_sample_ex(float* logits, int ldl, int V, int* tok, int* pos, int* gen, int ldg, int* n_gen,
-                            const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                            const void* params, void* ws, long long ws_bytes, hipStream_t st);
-CAIN_API int cain_logprob_rows(const float* logits, int ldl, int V, int M, const int* slot, const int* done,
-                               const int* topn, int nmax, const int* target, float* lse, float* lp, int* top_id,
-                               float* top_lp, hipStream_t st);
-CAIN_API int cain_logprob_pre(const float* logits, int ldl, int V, int M, const int* slot, const int* done,
-                              const int* topn, int nmax, const int* n_gen, const int* hist, int ldg, int* top_id,
-                              float* top_lp, void* keep, hipStream_t st);
-CAIN_API int cain_logprob_chosen(const float* logits, int ldl, int V, int M, const int* gen, int ldg, const void* keep,
-                                 float* lp, hipStream_t st);
-CAIN_API int cain_spec_draft(const CainSpec* s, int R, int T_max, const int* tok, const int* pos, const int* slot,
-                             const int* n_gen, const int* max_new, const int* done, const int* hist,
-                             const void* params, hipStream_t st);
-CAIN_API int cain_spec_accept(const CainSpec* s, int R, int T_max, int* tok, int* pos, const int* slot, int* n_gen,
-                              const int* max_new, int* done, int* hist, int* gen, int ldg, const void* params,
-                              hipStream_t st);
 
 extern "C" {
 
@@ -257,48 +185,45 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
   auto gemm = [&](const void* W, const void* W8, const void* ws, const void* X, int ldx, int K, int N, void* Y,
                   int ldy, const float* bias, int norm, const void* kc, const void* vc, int epi, int mf = MFMT_PLAN,
                   int tile0 = 0) -> int {
-    void* kcm = const_cast<void*>(kc);
-    void* vcm = const_cast<void*>(vc);
+    CainGemm g{};
+    g.W = W, g.sc = ws, g.X = X, g.ldx = ldx, g.K = K, g.N = N, g.M = M, g.Y = Y, g.ldy = ldy, g.bias = bias;
+    g.norm = norm, g.eps = d.eps, g.slot = r.slot, g.pos = r.pos, g.cos_t = d.cos_t, g.sin_t = d.sin_t;
+    g.kc = const_cast<void*>(kc), g.vtc = const_cast<void*>(vc);
+    g.H = d.H, g.Hkv = d.Hkv, g.hd = d.hd, g.T_max = d.T_max, g.epi = epi, g.tile0 = tile0;
     const bool gguf = d.wfmt == WFMT_Q4_0 || d.wfmt == WFMT_Q4_K;
-    if (gguf && mf == MFMT_Q6_K) {
-      // Q6_K (gemm_qstream.hip): ws = [int8 group scales: N K / 16 bytes][fp32 d: N K / 64 bytes][the fp32 norm gain]
-      const char* sc = static_cast<const char*>(ws);
-      const char* dd = sc + (size_t)N * K / 16;
-      const float* gain = d.q4_gain && norm ? reinterpret_cast<const float*>(dd + (size_t)N * K / 64) : nullptr;
-      return cain_gemm_q6(2, W, sc, dd, gain, X, ldx, K, N, M, Y, ldy, bias, norm, d.eps, r.slot, r.pos, d.cos_t,
-                          d.sin_t, kcm, vcm, d.H, d.Hkv, d.hd, d.T_max, epi, tile0, st);
-    }
-    if (tile0 != 0 || (mf != MFMT_PLAN && !(gguf && (mf == WFMT_Q4_0 || mf == WFMT_Q4_K)))) return -1;
+    const bool q6 = gguf && mf == MFMT_Q6_K;
+    if (!q6 && (tile0 != 0 || (mf != MFMT_PLAN && !(gguf && (mf == WFMT_Q4_0 || mf == WFMT_Q4_K))))) return -1;
     const int qf = gguf ? (mf == MFMT_PLAN ? d.wfmt : mf) : 0;
-    if (d.wfmt == WFMT_FP4 && d.x8 && (M > g_w4a8_min_rows || M > 64) && cain_w8a8_eligible(N, K, M)) {  // W4A8
-      CK(cain_quant_rows(X, ldx, K, M, d.x8, d.x8_ld, d.xs, norm, d.eps, st));
-      return cain_gemm_w4a8(W, ws, d.x8, d.x8_ld, d.xs, K, N, M, Y, ldy, bias, r.slot, r.pos, d.cos_t, d.sin_t, kcm,
-                            vcm, d.H, d.Hkv, d.hd, d.T_max, d.gemm_ws, d.gemm_ws_bytes, epi, st);
+    // W4A8 / W8A8: the rows quantised per row to fp8 for the scaled-MFMA wide kernels
+    auto a8 = [&]() -> int {
+      g.X = d.x8, g.ldx = d.x8_ld, g.xs = d.xs, g.ws = d.gemm_ws, g.ws_bytes = d.gemm_ws_bytes;
+      return cain_quant_rows(X, ldx, K, M, d.x8, d.x8_ld, d.xs, norm, d.eps, st);
+    };
+    if (d.wfmt == WFMT_FP4 && d.x8 && (M > g_w4a8_min_rows || M > 64) && cain_w8a8_eligible(N, K, M)) {
+      CK(a8());
+      return cain_gemm_mxfp4a8(&g, st);
     }
     if (gguf) {
-      // GGUF Q4_0 / Q4_K (gemm_qstream.hip): ws = [block scales: N K / 16 bytes][Q4_K: (d, dmin): N K / 64 bytes]
-      // [the fp32 norm gain over K, when the plan keeps gains unfolded (a GGUF file's exact values)]
-      const char* sc = static_cast<const char*>(ws);
-      const char* dd = sc + (size_t)N * K / 16;
-      const float* gain = d.q4_gain && norm ? reinterpret_cast<const float*>(dd + (qf == WFMT_Q4_K ? (size_t)N * K / 64 : 0))
-                                            : nullptr;
-      return cain_gemm_q4(qf == WFMT_Q4_K, W, sc, dd, gain, X, ldx, K, N, M, Y, ldy, bias, norm, d.eps, r.slot,
-                          r.pos, d.cos_t, d.sin_t, kcm, vcm, d.H, d.Hkv, d.hd, d.T_max, epi, st);
+      // ws = [scales: N K / 16 bytes (Q4: per block, Q6_K: int8 per group)][Q4_K: (d, dmin), Q6_K: fp32 d: N K / 64
+      // bytes][the fp32 norm gain over K, when the plan keeps gains unfolded (a GGUF file's exact values)]
+      const char* dd = static_cast<const char*>(ws) + (size_t)N * K / 16;
+      g.fmt = q6 ? 2 : qf == WFMT_Q4_K;
+      g.dd = dd;
+      if (d.q4_gain && norm) g.gain = reinterpret_cast<const float*>(dd + (g.fmt ? (size_t)N * K / 64 : 0));
+      return cain_gemm_gguf(&g, st);
     }
-    if (d.wfmt == WFMT_FP4)
-      return cain_gemm_w4_ex(W, ws, X, ldx, K, N, M, Y, ldy, bias, norm, d.eps, r.slot, r.pos, d.cos_t, d.sin_t, kcm,
-                             vcm, d.H, d.Hkv, d.hd, d.T_max, d.gemm_ws, d.gemm_ws_bytes, epi, st);
-    const float* wsf = static_cast<const float*>(ws);
-    if (d.wfmt == WFMT_FP8 && W8 && d.x8 && cain_w8a8_eligible(N, K, M)) {  // W8A8: per-row fp8 activations
-      CK(cain_quant_rows(X, ldx, K, M, d.x8, d.x8_ld, d.xs, norm, d.eps, st));
-      return cain_gemm_w8a8(W8, wsf, d.x8, d.x8_ld, d.xs, K, N, M, Y, ldy, bias, r.slot, r.pos, d.cos_t, d.sin_t, kcm,
-                            vcm, d.H, d.Hkv, d.hd, d.T_max, d.gemm_ws, d.gemm_ws_bytes, epi, st);
+    if (d.wfmt == WFMT_FP4) {
+      g.ws = d.gemm_ws, g.ws_bytes = d.gemm_ws_bytes;
+      return cain_gemm_mxfp4(&g, st);
     }
-    if (d.wfmt == WFMT_FP8)
-      return cain_gemm_w8(W, wsf, X, ldx, K, N, M, Y, ldy, bias, norm, d.eps, r.slot, r.pos, d.cos_t, d.sin_t, kcm, vcm,
-                          d.H, d.Hkv, d.hd, d.T_max, epi, st);
-    return cain_gemm(W, X, ldx, K, N, M, Y, ldy, bias, norm, d.eps, r.slot, r.pos, d.cos_t, d.sin_t, kcm, vcm, d.H,
-                     d.Hkv, d.hd, d.T_max, d.gemm_ws, d.gemm_ws_bytes, epi, d.waves, st);
+    if (d.wfmt == WFMT_FP8 && W8 && d.x8 && cain_w8a8_eligible(N, K, M)) {
+      CK(a8());
+      g.W = W8;
+      return cain_gemm_fp8a8(&g, st);
+    }
+    if (d.wfmt == WFMT_FP8) return cain_gemm_fp8(&g, st);
+    g.ws = d.gemm_ws, g.ws_bytes = d.gemm_ws_bytes, g.waves = d.waves;
+    return cain_gemm_bf16(&g, st);
   };
   CK(cain_embed(r.tok, d.embed, d.x, d.d, M, d.d, d.embed_scale, st));
   for (int l = 0; l < d.n_layers; ++l) {
@@ -534,7 +459,7 @@ static int device_cus() {
   return n;
 }
 
-extern "C" int cain_cu_budget() {
+CAIN_API int cain_cu_budget() {
   const int n = device_cus();
   return g_cu_budget > 0 && g_cu_budget < n ? g_cu_budget : n;
 }

@@ -12,7 +12,7 @@
 //                       first draft that differs, lane 0 commits t_0 .. t_a with the sampler's advance_row semantics.
 //
 // Integer work only, plain vector loads and stores, no atomics.
-#include "spec.h"
+#include "cain_api.h"
 
 #include <stdint.h>
 
@@ -174,10 +174,8 @@ int spec_ok(const CainSpec* s, int R, int T_max) {
 
 }  // namespace
 
-#define SPEC_API extern "C" __attribute__((visibility("default")))
-
 // Rows [0, R) of the decode state -> the expanded state of `s` (R (K + 1) rows), drafts into s->nd / s->draft.
-SPEC_API int cain_spec_draft(const CainSpec* s, int R, int T_max, const int* tok, const int* pos, const int* slot,
+CAIN_API int cain_spec_draft(const CainSpec* s, int R, int T_max, const int* tok, const int* pos, const int* slot,
                              const int* n_gen, const int* max_new, const int* done, const int* hist,
                              const void* params, hipStream_t st) {
   if (!spec_ok(s, R, T_max) || !tok || !pos || !slot || !n_gen || !max_new || !done || !hist || !params) return -1;
@@ -187,7 +185,7 @@ SPEC_API int cain_spec_draft(const CainSpec* s, int R, int T_max, const int* tok
 }
 
 // After the sampler ran over the expanded rows: commit each sequence's accepted tokens to rows [0, R).
-SPEC_API int cain_spec_accept(const CainSpec* s, int R, int T_max, int* tok, int* pos, const int* slot, int* n_gen,
+CAIN_API int cain_spec_accept(const CainSpec* s, int R, int T_max, int* tok, int* pos, const int* slot, int* n_gen,
                               const int* max_new, int* done, int* hist, int* gen, int ldg, const void* params,
                               hipStream_t st) {
   if (!spec_ok(s, R, T_max) || !tok || !pos || !slot || !n_gen || !max_new || !done || !hist || !gen || ldg < 1 ||
@@ -198,4 +196,4 @@ SPEC_API int cain_spec_accept(const CainSpec* s, int R, int T_max, int* tok, int
   return int(hipGetLastError());
 }
 
-SPEC_API int cain_spec_size() { return int(sizeof(CainSpec)); }
+CAIN_API int cain_spec_size() { return int(sizeof(CainSpec)); }

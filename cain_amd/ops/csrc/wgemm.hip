@@ -671,7 +671,6 @@ CAIN_API void cain_wgemm_clear_shapes() { g_wg_nshapes = 0; }
 // Timestamp buffer of the diagnostic variant 7 (>= grid * 16 uint64; tools/wgemm_trace.py).
 static unsigned long long* g_wg_stamps = nullptr;
 CAIN_API void cain_wgemm_set_stamps(void* p) { g_wg_stamps = static_cast<unsigned long long*>(p); }
-CAIN_API int cain_wgemm_eligible(int N, int K, int M);
 // The plan the next launch of this shape would use: ks * 64 + variant (tests, tools).
 CAIN_API int cain_wgemm_plan(int N, int K, int M) {
   if (!cain_wgemm_eligible(N, K, M)) return -1;

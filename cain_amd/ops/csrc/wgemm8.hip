@@ -341,26 +341,19 @@ CAIN_API int cain_quant_rows(const void* x, int ldx, int K, int M, void* x8, int
 
 namespace {
 
-int w8a8_run(bool fp4, const void* Wp8, const void* wscale, const void* X8, int ld8, const float* xs, int K, int N,
-             int M, void* Y, int ldy, const float* bias, const int* slot, const int* pos, const float* cos_t,
-             const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd, int T_max, void* ws, long long ws_bytes,
-             int epi_flags, hipStream_t st) {
-  const int epi = epi_flags & EPI_MASK;
-  if (!cain_w8a8_eligible(N, K, M) || ld8 % 16) return -1;
-  if (epi == EPI_QKV_ROPE && (hd % 16 || (hd / 2) % 8)) return -1;
+// X / ldx of the record: the e4m3 rows of cain_quant_rows and their stride in bytes (norm and eps went into xs)
+int w8a8_run(bool fp4, const CainGemm& g, hipStream_t st) {
+  const int K = g.K, N = g.N, M = g.M, epi = g.epi & EPI_MASK;
+  void* const ws = g.ws;
+  if (!cain_w8a8_eligible(N, K, M) || g.ldx % 16) return -1;
+  GemmArgs a;
+  if (!gemm_args(g, a)) return -1;
   const W8Plan p = w8_plan(N, K, M);
-  if (p.ks > 1 && (!ws || W8_SLAB_OFFSET + (long long)(p.part_floats * sizeof(float)) > ws_bytes)) return -1;
-  GemmArgs a{};
-  a.Wp = reinterpret_cast<const bf16x8*>(Wp8);
-  a.X = reinterpret_cast<const __bf16*>(X8);
-  a.ldx = ld8, a.K = K, a.N = N, a.M = M, a.Y = Y, a.ldy = ldy, a.bias = bias;
-  a.slot = slot, a.pos = pos, a.cos_t = cos_t, a.sin_t = sin_t;
-  a.kc = reinterpret_cast<__bf16*>(kc), a.vtc = reinterpret_cast<__bf16*>(vtc);
-  a.H = H, a.Hkv = Hkv, a.hd = hd, a.T_max = T_max, a.kv8 = (epi_flags & EPI_KV_FP8) ? 1 : 0;
+  if (p.ks > 1 && (!ws || W8_SLAB_OFFSET + (long long)(p.part_floats * sizeof(float)) > g.ws_bytes)) return -1;
   WgArgs w{};
   w.ks = p.ks, w.kst = p.kst, w.part = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + W8_SLAB_OFFSET) : nullptr;
   w.xcd_blk = p.ks > 1 && p.nblk % 8 == 0;  // XCD-local split-K (wgemm_ring.h wg_block_of)
-  const W8Scales q{xs, static_cast<const float*>(wscale)};
+  const W8Scales q{g.xs, static_cast<const float*>(g.sc)};
   hipError_t e;
   if (fp4) e = p.bm == 256 ? w8_launch_e<256, true>(epi, a, w, q, p, st) : w8_launch_e<128, true>(epi, a, w, q, p, st);
   else e = p.bm == 256 ? w8_launch_e<256>(epi, a, w, q, p, st) : w8_launch_e<128>(epi, a, w, q, p, st);
@@ -369,23 +362,11 @@ int w8a8_run(bool fp4, const void* Wp8, const void* wscale, const void* X8, int 
 
 }  // namespace
 
-// Y = epi(xs[m] * ws[n] * X8 . W8^T).  Wp8: pack_mfma_a_fp8_k128; X8 [M][ld8] e4m3 rows (cain_quant_rows);
-// ws: >= cain_w8a8_ws_bytes of scratch; the rest as cain_gemm (gemm.hip), including the EPI_KV_FP8 flag.
-CAIN_API int cain_gemm_w8a8(const void* Wp8, const float* wscale, const void* X8, int ld8, const float* xs, int K,
-                            int N, int M, void* Y, int ldy, const float* bias, const int* slot, const int* pos,
-                            const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                            int T_max, void* ws, long long ws_bytes, int epi_flags, hipStream_t st) {
-  return w8a8_run(false, Wp8, wscale, X8, ld8, xs, K, N, M, Y, ldy, bias, slot, pos, cos_t, sin_t, kc, vtc, H, Hkv, hd,
-                  T_max, ws, ws_bytes, epi_flags, st);
-}
+// Y = epi(xs[m] * sc[n] * X8 . W8^T).  W: pack_mfma_a_fp8_k128; X [M][ldx] e4m3 rows (cain_quant_rows);
+// ws: >= cain_w8a8_ws_bytes of scratch; the rest as cain_gemm_bf16 (gemm.hip), including the EPI_KV_FP8 flag.
+CAIN_API int cain_gemm_fp8a8(const CainGemm* g, hipStream_t st) { return w8a8_run(false, *g, st); }
 
-// W4A8: Y = epi(xs[m] * X8 . W^T) with MXFP4 weights in the few-row kernel's packing (pack_mxfp4: Wq
-// [N/16][K/128][64][16] e2m1 bytes, wsc [N/16][K/128][64] e8m0 bytes); same shapes, workspace and epilogues as
-// cain_gemm_w8a8 (cain_w8a8_eligible, cain_w8a8_ws_bytes).
-CAIN_API int cain_gemm_w4a8(const void* Wq, const void* wsc, const void* X8, int ld8, const float* xs, int K, int N,
-                            int M, void* Y, int ldy, const float* bias, const int* slot, const int* pos,
-                            const float* cos_t, const float* sin_t, void* kc, void* vtc, int H, int Hkv, int hd,
-                            int T_max, void* ws, long long ws_bytes, int epi_flags, hipStream_t st) {
-  return w8a8_run(true, Wq, wsc, X8, ld8, xs, K, N, M, Y, ldy, bias, slot, pos, cos_t, sin_t, kc, vtc, H, Hkv, hd,
-                  T_max, ws, ws_bytes, epi_flags, st);
-}
+// W4A8: Y = epi(xs[m] * X8 . W^T) with MXFP4 weights in the few-row kernel's packing (pack_mxfp4: W
+// [N/16][K/128][64][16] e2m1 bytes, sc [N/16][K/128][64] e8m0 bytes); same shapes, workspace and epilogues as
+// cain_gemm_fp8a8 (cain_w8a8_eligible, cain_w8a8_ws_bytes).
+CAIN_API int cain_gemm_mxfp4a8(const CainGemm* g, hipStream_t st) { return w8a8_run(true, *g, st); }

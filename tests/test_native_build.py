@@ -7,7 +7,8 @@ from cain_amd.energy import native
 
 def test_kernel_library_loads_and_binds():
     lib = ops.load()
-    for sym in ("cain_skinny_gemm_ex", "cain_gemm", "cain_gemm_ws_bytes", "cain_rmsnorm", "cain_embed", "cain_attention", "cain_sample",
+    for sym in ("cain_gemm_bf16", "cain_gemm_size", "cain_gemm_fp8", "cain_gemm_mxfp4", "cain_gemm_gguf", "cain_gemm_fp8a8",
+                "cain_gemm_mxfp4a8", "cain_gemm_ws_bytes", "cain_rmsnorm", "cain_embed", "cain_attention", "cain_sample",
                 "cain_plan_create", "cain_plan_forward", "cain_plan_capture", "cain_graph_launch",
                 "cain_graph_destroy", "cain_sample_params_size", "cain_rows_size", "cain_plan_desc_size"):
         assert hasattr(lib, sym), sym
@@ -21,6 +22,7 @@ def test_struct_layouts_match_native():
     assert lib.cain_rows_size() == ctypes.sizeof(_CainRows)
     assert lib.cain_layer_size() == ctypes.sizeof(_CainLayer)
     assert lib.cain_sample_params_size() == ops.SAMPLE_BYTES == 48
+    assert lib.cain_gemm_size() == ctypes.sizeof(ops.CainGemm)
 
 
 def test_energy_library_loads_without_gpu():
@@ -36,6 +38,6 @@ def test_default_kernel_library_links_no_vendor_gemm():
 
     lib = ops.load()
     assert not hasattr(lib, "cain_lt_gemm") and not hasattr(lib, "cain_set_lt_api")
-    assert hasattr(lib, "cain_gemm_w4") and not hasattr(lib, "cain_front")
+    assert hasattr(lib, "cain_gemm_mxfp4") and not hasattr(lib, "cain_front")
     needed = subprocess.run(["readelf", "-d", str(ops.LIB_PATH)], capture_output=True, text=True).stdout
     assert "hipblaslt" not in needed.lower() and "rocblas" not in needed.lower(), needed

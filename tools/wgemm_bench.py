@@ -8,7 +8,7 @@ us per call and effective weight TB/s; plus the numerics of the wide kernel vs a
 
     python tools/wgemm_bench.py [--model llama3.1:8b] [--rows 128,256] [--iters 20] [--weights bf16,fp8,fp4]
 
---weights fp8 / fp4 time the W8A8 / W4A8 wide kernels (csrc/wgemm8.hip: cain_gemm_w8a8 / cain_gemm_w4a8 on rows
+--weights fp8 / fp4 time the W8A8 / W4A8 wide kernels (csrc/wgemm8.hip: cain_gemm_fp8a8 / cain_gemm_mxfp4a8 on rows
 quantised once, outside the timed loop) the same way: one JSON line per (shape, M) with "weights" and "wide_us".
 """
 from __future__ import annotations
@@ -48,7 +48,7 @@ def time_a8(ns, lib, fmt, name, N, K, epi, norm, rows, dev):
     else:
         one = pack_mxfp4(*quantize_mxfp4(W))
     packs = [one] + [tuple(t.clone() for t in one) for _ in range(ncopy - 1)]
-    fn = lib.cain_gemm_w8a8 if fmt == "fp8" else lib.cain_gemm_w4a8
+    fn = lib.cain_gemm_fp8a8 if fmt == "fp8" else lib.cain_gemm_mxfp4a8
     for M in rows:
         x = (2 * torch.randn(M, K, device=dev)).bfloat16()
         x8, xs = ops.quant_rows(x, norm, 1e-6)
@@ -58,10 +58,12 @@ def time_a8(ns, lib, fmt, name, N, K, epi, norm, rows, dev):
         ws = torch.zeros(max(nbytes, 16), device=dev, dtype=torch.uint8)
         st = ops._stream()
 
+        g = ops.CainGemm(X=x8.data_ptr(), ldx=K, xs=xs.data_ptr(), K=K, N=N, M=M, Y=out.data_ptr(), ldy=out.stride(0),
+                         ws=ws.data_ptr(), ws_bytes=nbytes, epi=epi)
+
         def run(i):
-            wq, sc = packs[i % ncopy]
-            rc = fn(ops._p(wq), ops._p(sc), ops._p(x8), K, ops._p(xs), K, N, M, ops._p(out), out.stride(0), None, None,
-                    None, None, None, None, None, 0, 0, 0, 0, ops._p(ws), nbytes, epi, st)
+            g.W, g.sc = (t.data_ptr() for t in packs[i % ncopy])
+            rc = fn(g, st)
             assert rc == 0, rc
 
         for i in range(3):
