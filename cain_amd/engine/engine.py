@@ -30,6 +30,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import threading
 import time
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Union
@@ -40,6 +41,7 @@ import torch
 from ..models.config import ModelConfig, get_config, rope_inv_freq
 from ..models.hf import checkpoint_for, load_hf_weights, load_pretrained, load_tokenizer
 from ..models.tokenizer import get_tokenizer
+from . import jsonmode
 from .speculative import K_MAX, SeqState
 from .speculative import draft as spec_draft_host
 from ..models.weights import WEIGHT_DTYPES, ModelWeights, pack_for_engine, random_weights, roundtrip_weights
@@ -83,6 +85,10 @@ class GenResult:
     draft_accepted: Optional[int] = None
     decode_steps: Optional[int] = None
     step_tokens: Optional[List[int]] = None
+    # JSON mode (None: the row was not in it): "done" -- the top-level object closed, on the row's last token;
+    # "open" -- the budget ran out inside the document (the text is a viable prefix); "fail" -- the sampler drew a
+    # masked token (a rounding of its last prefix sum), which was taken back
+    json_state: Optional[str] = None
 
     @property
     def prompt_eval_count(self) -> int:
@@ -172,6 +178,21 @@ class _CainPlanDesc(ctypes.Structure):
 class _CainRows(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_void_p) for n in ("tok", "pos", "slot", "n_gen", "max_new", "done", "hist", "gen")]
                 + [("ldg", ctypes.c_int), ("sample_params", ctypes.c_void_p)])
+
+
+def _want_format(format, opts: Sequence[Optional[Dict]], B: int) -> List[bool]:
+    """Per row: JSON mode or not, from ``format`` (None / "" off, "json" on; one value or one per row) or, where
+    that leaves a row off, the row's option key ``"format"``."""
+    fs = list(format) if isinstance(format, (list, tuple)) else [format] * B
+    if len(fs) != B:
+        raise ValueError(f"format for {len(fs)} rows, {B} prompts")
+    out = []
+    for i, f in enumerate(fs):
+        f = f or (opts[i].get("format") if i < len(opts) and opts[i] else None)
+        if f not in (None, "", "json"):
+            raise ValueError(f'format must be "json" or absent, got {f!r}')
+        out.append(f == "json")
+    return out
 
 
 class _CainLogprob(ctypes.Structure):  # runtime.hip CainLogprob
@@ -352,6 +373,17 @@ def taken_record(record: Sequence[int], n: int, prompt: Sequence[int]) -> List[i
     return list(record[:n]) + [int(t) for t in prompt[n:len(prompt) - 1]]
 
 
+class _PieceDecoder:
+    """``decode`` by the byte pieces of ``DecodeEngine.set_json_vocab`` (a character cut at the end decodes to
+    U+FFFD, which ``StreamDecoder`` holds back)."""
+
+    def __init__(self, eng: "DecodeEngine"):
+        self.eng = eng
+
+    def decode(self, ids) -> str:
+        return self.eng._json_text([int(t) for t in ids])
+
+
 class DecodeEngine:
     @classmethod
     def from_pretrained(cls, path: str, device: Union[str, torch.device] = "cuda", name: Optional[str] = None,
@@ -403,6 +435,11 @@ class DecodeEngine:
         batch then holds at most ``rows per forward // (K + 1)`` sequences; not together with ``prefix_cache`` or
         ``logprobs``."""
         self.cfg = get_config(model) if isinstance(model, str) else model
+        self._json_pieces: Optional[List[bytes]] = None  # JSON mode's vocabulary, made at first use (_json_vocab)
+        self._json_lock = threading.Lock()
+        self._json_custom = False  # ... given by set_json_vocab: the text of a JSON row is spelt with it
+        self._gr: Optional[Dict] = None  # JSON mode's device buffers (hip backend), made at first use (_gr_bufs)
+        self._last_json: Optional[List[Optional[str]]] = None
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
         if weight_dtype == "fp4" and any(k % 128 for k in (self.cfg.d_model, self.cfg.q_dim, self.cfg.ffn)):
@@ -665,12 +702,86 @@ class DecodeEngine:
                                                   _ptr(b["target"]))
         return q
 
-    def _forward(self, M: int, rows, want_logits: bool, want_sample: bool, lp: Optional[_CainLogprob] = None) -> None:
+    # ---------------------------------------------------------------- JSON mode
+    def set_json_vocab(self, pieces: Sequence[bytes]) -> None:
+        """The bytes each token id appends to the output, for JSON mode (``generate(format="json")``), instead of the
+        tokenizer's own pieces: random-init tags have a synthetic tokenizer with no punctuation, so tests and
+        benchmarks on random weights supply a vocabulary.  Ids past ``len(pieces)`` are empty (never allowed); the
+        text of a JSON-mode row is then these bytes.  Raises ValueError when the vocabulary cannot spell JSON."""
+        pieces = [bytes(p) for p in pieces]
+        if len(pieces) > self.cfg.vocab:
+            raise ValueError(f"{len(pieces)} pieces for a vocabulary of {self.cfg.vocab}")
+        pieces += [b""] * (self.cfg.vocab - len(pieces))
+        jsonmode.check_vocabulary(pieces)
+        with self._json_lock:
+            self._json_pieces, self._json_custom = pieces, True
+        self._gr = None
+        for key in [k for k in getattr(self, "_graphs", {}) if "gr" in k]:  # graphs that captured the old table
+            self.lib.cain_graph_destroy(ctypes.c_void_p(self._graphs.pop(key)))
+
+    def _json_vocab(self) -> List[bytes]:
+        with self._json_lock:  # (a server's handler threads and its scheduler thread may both ask first)
+            if self._json_pieces is None:
+                pieces = jsonmode.token_bytes(self.tokenizer, self.cfg.vocab)
+                jsonmode.check_vocabulary(pieces)
+                self._json_pieces = pieces
+            return self._json_pieces
+
+    def _json_text(self, toks: Sequence[int]) -> str:
+        return b"".join(self._json_pieces[t] for t in toks).decode("utf-8", errors="replace")
+
+    def text_decoder(self, json_row: bool = False):
+        """What turns a row's token ids into text (``.decode(ids)``): the tokenizer, or -- for a JSON-mode row of an
+        engine whose vocabulary ``set_json_vocab`` supplied -- that vocabulary's bytes."""
+        return _PieceDecoder(self) if json_row and self._json_custom else self.tokenizer
+
+    def _gr_bufs(self) -> Dict:
+        """Device buffers of JSON mode (csrc/grammar.hip): per decode row the mode flag and the automaton state, and
+        the vocabulary's piece table."""
+        if self._gr is None:
+            from .. import ops
+
+            R = self.gen.shape[0]
+            self._gr = dict(ops.json_table(self._json_vocab(), self.device),
+                            gram_on=torch.zeros(R, device=self.device, dtype=torch.int32),
+                            gstate=torch.zeros(R, 4, device=self.device, dtype=torch.int32))
+        return self._gr
+
+    def _gr_struct(self):
+        from .. import ops
+
+        b, g = self._gr_bufs(), ops.CainGrammar()
+        g.gram_on, g.gstate = _ptr(b["gram_on"]), _ptr(b["gstate"])
+        g.piece_off, g.piece_bytes = _ptr(b["piece_off"]), _ptr(b["piece_bytes"])
+        return g
+
+    def _gr_begin(self, rows: slice, fmt: Sequence[bool]) -> None:
+        """Decode rows ``rows`` start requests: JSON mode per ``fmt``, every state at the start of a document."""
+        b = self._gr_bufs()
+        b["gram_on"][rows].copy_(torch.tensor([int(f) for f in fmt], dtype=torch.int32))
+        b["gstate"][rows].zero_()  # jsonmode.INITIAL
+
+    def _gr_states(self, n: int, fmt: Sequence[bool]) -> List[Optional[str]]:
+        from .. import ops
+
+        names = {jsonmode.DONE: "done", jsonmode.FAIL: "fail"}
+        st = ops.json_states_host(self._gr_bufs()["gstate"][:n])
+        return [names.get(jsonmode.sid_of(s), "open") if f else None for s, f in zip(st, fmt)]
+
+    def _forward(self, M: int, rows, want_logits: bool, want_sample: bool, lp: Optional[_CainLogprob] = None,
+                 gr=None) -> None:
         rs = self._rows_struct(rows, want_sample)
         plan = self._plan(M)
         _set_cu_budget(self.lib, self.cu_limit)  # launch sizing for this engine's stream (0: whole device)
         try:
-            if lp is not None:
+            if gr is not None:
+                from .. import ops
+
+                rc = ops.load_grammar().cain_plan_forward_gr(
+                    ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits), int(want_sample),
+                    ctypes.byref(lp) if lp is not None else None, ctypes.byref(gr),
+                    ctypes.c_void_p(self.stream.cuda_stream))
+            elif lp is not None:
                 rc = self.lib.cain_plan_forward_lp(ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits),
                                                    int(want_sample), ctypes.byref(lp),
                                                    ctypes.c_void_p(self.stream.cuda_stream))
@@ -683,10 +794,11 @@ class DecodeEngine:
             where = self.lib.cain_plan_last_failure()
             raise RuntimeError(f"cain_plan_forward failed rc={rc}" + (f" at {where.decode()}" if where else ""))
 
-    def _graph(self, M: int, steps: int, lp: bool = False) -> int:
+    def _graph(self, M: int, steps: int, lp: bool = False, gr: bool = False) -> int:
         """``lp``: the steps also compute token log-probabilities (for the rows whose ``topn`` says so when the graph
-        runs) -- a cache entry of its own; without it the graph is launch for launch the one it always was."""
-        key = (M, steps, "lp") if lp else (M, steps)
+        runs) -- a cache entry of its own; without it the graph is launch for launch the one it always was.
+        ``gr``: the steps run JSON mode's mask and advance (for the rows whose ``gram_on`` says so), likewise."""
+        key = (M, steps) + (("lp",) if lp else ()) + (("gr",) if gr else ())
         g = self._graphs.get(key)
         if g is None:
             rs = self._rows_struct(self.rows, True)
@@ -694,7 +806,14 @@ class DecodeEngine:
             plan = self._plan(M)
             _set_cu_budget(self.lib, self.cu_limit)
             try:
-                if lp:
+                if gr:
+                    from .. import ops
+
+                    q, gs = (self._lp_struct(True) if lp else None), self._gr_struct()
+                    g = ops.load_grammar().cain_plan_capture_gr(
+                        ctypes.c_void_p(plan), M, ctypes.byref(rs), steps, ctypes.byref(q) if lp else None,
+                        ctypes.byref(gs), ctypes.c_void_p(self.stream.cuda_stream), ctypes.byref(err))
+                elif lp:
                     q = self._lp_struct(True)
                     g = self.lib.cain_plan_capture_lp(ctypes.c_void_p(plan), M, ctypes.byref(rs), steps,
                                                       ctypes.byref(q), ctypes.c_void_p(self.stream.cuda_stream),
@@ -815,7 +934,8 @@ class DecodeEngine:
                  on_tokens=None, context: Optional[Sequence[Optional[Sequence[int]]]] = None,
                  logprobs: Union[bool, Sequence[bool]] = False,
                  top_logprobs: Union[int, Sequence[int]] = 0,
-                 drafts: Optional[Sequence[Optional[Sequence[int]]]] = None) -> List[GenResult]:
+                 drafts: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                 format: Union[None, str, Sequence[Optional[str]]] = None) -> List[GenResult]:
         """Generate for a batch of prompts (ids or text).  ``on_tokens(list_per_row)`` streams newly
         generated ids every ``steps_per_graph`` decode steps (and stops early once every row is done).
         ``context[i]``: token ids prepended to row i's encoded prompt (Ollama's ``context`` of an earlier answer).
@@ -826,12 +946,25 @@ class DecodeEngine:
         decode graphs (csrc/logprob.hip); the tokens are the same with and without.  With logprobs asked for,
         ``on_tokens`` gets a second argument: per row ``(logprobs, top_logprobs)`` of the new tokens, or None.
         ``drafts`` (speculative engines): per row the draft token of every generated index (a negative id ends a
-        step's draft; None: no drafts for that row); this call then verifies these instead of the n-gram lookup's."""
+        step's draft; None: no drafts for that row); this call then verifies these instead of the n-gram lookup's.
+        ``format="json"`` (one value or one per row; or the per-row option key ``"format"``): Ollama's JSON mode --
+        the row's generated tokens are constrained, step by step, to those whose bytes continue an RFC 8259 document
+        whose top-level value is an object (engine/jsonmode.py; on the HIP backend a mask on the logits inside the
+        decode graphs, csrc/grammar.hip).  The row ends on the token that closes the object (``done_reason`` "stop",
+        no EOS needed); a row whose budget runs out first holds a viable prefix ("length").  The state starts fresh
+        per request; the prompt is not constrained.  Not together with speculative decoding."""
         prompts = list(prompts)
         B = len(prompts)
         if B == 0:
             return []
         want = _want_logprobs(logprobs, top_logprobs, B)
+        opts = list(options) if isinstance(options, (list, tuple)) else [options] * B
+        fmt = _want_format(format, opts, B)
+        if self.speculative and any(fmt):
+            raise ValueError("format cannot be combined with speculative decoding (the K + 1 expanded rows would "
+                             "each need the state after their drafts)")
+        if any(fmt):
+            self._json_vocab()  # (ValueError: the vocabulary cannot spell JSON)
         if self.speculative and any(w >= 0 for w in want):
             raise ValueError("logprobs cannot be combined with speculative decoding")
         if drafts is not None and not self.speculative:
@@ -847,14 +980,14 @@ class DecodeEngine:
                 out += self.generate(prompts[sl], nps, ops_, use_graph, on_tokens,
                                      context[sl] if context is not None else None,
                                      [w >= 0 for w in want[sl]], [max(w, 0) for w in want[sl]],
-                                     drafts[sl] if drafts is not None else None)
+                                     drafts[sl] if drafts is not None else None,
+                                     ["json" if f else None for f in fmt[sl]])
             return out
         if context is not None and len(context) != B:
             raise ValueError(f"{len(context)} contexts for {B} prompts")
         ids = [([int(t) for t in context[i]] if context is not None and context[i] else []) + self.encode(p)
                or [self.cfg.bos_id] for i, p in enumerate(prompts)]
         nps = [int(num_predict)] * B if isinstance(num_predict, int) else [int(x) for x in num_predict]
-        opts = list(options) if isinstance(options, (list, tuple)) else [options] * B
         row_opts = [_row_options(o, self.cfg, i, self.seed) for i, o in enumerate(opts)]
         for i in range(B):
             budget = self.T_max - len(ids[i])
@@ -864,17 +997,18 @@ class DecodeEngine:
         t0 = time.perf_counter_ns()
         lps = None  # per row (logprobs, top_logprobs) or None
         self._last_spec = None
+        self._last_json = None
         if self.backend == "torch" and self.speculative:
             gen, t_pref, t_dec = self._generate_torch_spec(ids, nps, row_opts, drafts)
             if on_tokens is not None:
                 on_tokens(gen)
         elif self.backend == "torch":
-            gen, t_pref, t_dec, lps = self._generate_torch(ids, nps, row_opts, want)
+            gen, t_pref, t_dec, lps = self._generate_torch(ids, nps, row_opts, want, fmt)
             if on_tokens is not None:
                 on_tokens(gen, lps) if lps is not None else on_tokens(gen)
         else:
             gen, t_pref, t_dec, lps = self._generate_hip(ids, nps, row_opts, use_graph, on_tokens, want=want,
-                                                         drafts=drafts)
+                                                         drafts=drafts, fmt=fmt)
         total = time.perf_counter_ns() - t0
         load = self.load_duration_ns if self._first_call else 0
         self._first_call = False
@@ -883,8 +1017,10 @@ class DecodeEngine:
         out = []
         for i in range(B):
             toks = gen[i]
-            reason = "stop" if _stopped(toks, row_opts[i]) else "length"
-            out.append(GenResult(self.cfg.name, ids[i], toks, self.tokenizer.decode(toks), reason,
+            js = self._last_json[i] if self._last_json is not None else None
+            reason = "stop" if _stopped(toks, row_opts[i]) or js == "done" else "length"
+            text = self._json_text(toks) if js is not None and self._json_custom else self.tokenizer.decode(toks)
+            out.append(GenResult(self.cfg.name, ids[i], toks, text, reason, json_state=js,
                                  load_duration_ns=load, prompt_eval_duration_ns=t_pref,
                                  eval_duration_ns=int(t_dec * len(toks) / max(1, steps)),
                                  total_duration_ns=total + load))
@@ -907,12 +1043,13 @@ class DecodeEngine:
         return lp, [list(zip(a, c)) for a, c in zip(ti, tl)]
 
     def _generate_hip(self, ids, nps, row_opts, use_graph, on_tokens=None, check_every: int = 1, want=None,
-                      drafts=None):
+                      drafts=None, fmt=None):
         from .. import ops
 
         dev = self.device
         B = len(ids)
         with_lp = want is not None and any(w >= 0 for w in want)
+        with_gr = fmt is not None and any(fmt)  # some row in JSON mode: the graphs with the mask and the advance
         spec = self.speculative > 0  # K + 1 rows per sequence and step: speculative graphs, done polled per chunk
         spec_mode = int(drafts is not None)
         self._forget_slots(range(B))
@@ -935,6 +1072,10 @@ class DecodeEngine:
                 lq = self._lp_struct(True, max(want))
             if spec:
                 self._spec_begin(range(B), range(B), ids, drafts)
+            gq = None
+            if with_gr:
+                self._gr_begin(slice(0, B), fmt)
+                gq = self._gr_struct()
             self.stream.synchronize()
             t1 = time.perf_counter_ns()
             steps = max(nps)
@@ -947,13 +1088,16 @@ class DecodeEngine:
                     return
                 if not use_graph:
                     for _ in range(nsteps):
-                        if lq is None:  # (the call it always was: wrappers of _forward see the same arguments)
+                        if gq is not None:
+                            self._forward(B, r, want_logits=True, want_sample=True, lp=lq, gr=gq)
+                        elif lq is None:  # (the call it always was: wrappers of _forward see the same arguments)
                             self._forward(B, r, want_logits=True, want_sample=True)
                         else:
                             self._forward(B, r, want_logits=True, want_sample=True, lp=lq)
                     return
                 k = self.steps_per_graph
-                graph = (lambda n: self._graph_spec(B, n, spec_mode)) if spec else (lambda n: self._graph(B, n, with_lp))
+                graph = (lambda n: self._graph_spec(B, n, spec_mode)) if spec else \
+                    (lambda n: self._graph(B, n, with_lp, with_gr) if with_gr else self._graph(B, n, with_lp))
                 g = graph(k) if nsteps >= k else None
                 for _ in range(nsteps // k):
                     rc = self.lib.cain_graph_launch(ctypes.c_void_p(g), stream_h)
@@ -972,7 +1116,9 @@ class DecodeEngine:
             done_steps = 1
             emitted = [0] * B
             # (speculative: a step commits up to K + 1 tokens, so rows finish in fewer steps than tokens)
-            watch = spec or on_tokens is not None or any(o["eos_id"] >= 0 or o["stop"] for o in row_opts)
+            # (JSON mode: a row ends when its object closes)
+            watch = spec or with_gr or on_tokens is not None or \
+                any(o["eos_id"] >= 0 or o["stop"] for o in row_opts)
             chunk = self.steps_per_graph * max(1, int(check_every))
 
             def emit(new, ng) -> None:
@@ -1007,6 +1153,8 @@ class DecodeEngine:
                    for i in range(B)] if with_lp else None
             if spec:
                 self._last_spec = [self._spec_stats(i) for i in range(B)]
+            if with_gr:
+                self._last_json = self._gr_states(B, fmt)
             t2 = time.perf_counter_ns()
         self.last_ttft_ns = t_first - t0
         return [gen[i, : n_gen[i]].tolist() for i in range(B)], t1 - t0, t2 - t1, lps
@@ -1122,11 +1270,16 @@ class DecodeEngine:
             raise RuntimeError("continuous batching needs the hip backend")
         return ContinuousBatch(self)
 
-    def _generate_torch(self, ids, nps, row_opts, want=None):
+    def _generate_torch(self, ids, nps, row_opts, want=None, fmt=None):
         """Oracle backend with a KV cache (one token of compute per step), sampled on the host; logprobs (``want``
-        per row: -1 or the number of alternatives) by ``logprob_host`` of the same logits."""
+        per row: -1 or the number of alternatives) by ``logprob_host`` of the same logits.  JSON mode (``fmt`` per
+        row): the Python automaton masks the logits before the sampler with the device's values and ends the row by
+        the device's rule (engine/jsonmode.py)."""
         t0 = time.perf_counter_ns()
         gens = []
+        with_gr = fmt is not None and any(fmt)
+        pieces = self._json_vocab() if with_gr else None
+        jstates: List[Optional[str]] = [None] * len(ids)
         with_lp = want is not None and any(w >= 0 for w in want)
         lps: list = [([], []) if with_lp and want[i] >= 0 else None for i in range(len(ids))]
         for i, p in enumerate(ids):
@@ -1135,18 +1288,30 @@ class DecodeEngine:
             out = []
             cache: list = []
             step = torch.tensor([list(p)], device=self.device)
+            js = jsonmode.INITIAL if with_gr and fmt[i] else None
             for _ in range(nps[i]):
                 logits = self.ref.forward(step, cache=cache, last_only=True)[0, -1].float().cpu()
-                nxt = sample_host(logits, out, o, rng)
+                if js is None:
+                    nxt = sample_host(logits, out, o, rng)
+                else:  # (logprobs below stay those of the raw logits)
+                    masked = jsonmode.mask_logits_host(logits.numpy().copy(), js, pieces)
+                    nxt = sample_host(torch.from_numpy(masked), out, o, rng)
+                    js, ok = jsonmode.advance(js, pieces[nxt])
+                    if not ok:  # a masked token drawn: taken back, the row ends
+                        break
                 if lps[i] is not None:
                     ls, top = logprob_host(logits, want[i])
                     lps[i][0].append(float(ls[nxt]))
                     lps[i][1].append(top)
                 out.append(nxt)
                 step = torch.tensor([[nxt]], device=self.device)
-                if _stopped(out, o):
+                if _stopped(out, o) or (js is not None and jsonmode.sid_of(js) == jsonmode.DONE):
                     break
+            if js is not None:
+                jstates[i] = {jsonmode.DONE: "done", jsonmode.FAIL: "fail"}.get(jsonmode.sid_of(js), "open")
             gens.append(out)
+        if with_gr:
+            self._last_json = jstates
         t1 = time.perf_counter_ns()
         return gens, 0, t1 - t0, lps if with_lp else None
 
@@ -1255,6 +1420,7 @@ class ContinuousBatch:
         self.options: List[Dict] = []
         self.reused: List[int] = []  # per live row: leading prompt tokens its slot already held at admit
         self.want: List[int] = []  # per live row: -1 (no logprobs) or its number of top_logprobs
+        self.fmt: List[bool] = []  # per live row: JSON mode
         # prefix-cache bookkeeping per live row (engine.slot_tokens): steps run since admit, the newest polled
         # token (its KV is not written yet), done at the last poll, last position already dropped from the record
         self._steps: List[int] = []
@@ -1263,7 +1429,8 @@ class ContinuousBatch:
         self._trimmed: List[bool] = []
 
     def _row_lists(self):
-        return (self.row_slot, self.emitted, self.prompt_tokens, self.options, self.reused, self.want, self._steps,
+        return (self.row_slot, self.emitted, self.prompt_tokens, self.options, self.reused, self.want, self.fmt,
+                self._steps,
                 self._pending, self._done, self._trimmed)
 
     def _trim_idled(self) -> None:
@@ -1284,9 +1451,12 @@ class ContinuousBatch:
 
     def admit(self, prompts: Sequence[Union[str, Sequence[int]]], num_predict: Sequence[int],
               options: Sequence[Optional[Dict]], logprobs: Union[bool, Sequence[bool]] = False,
-              top_logprobs: Union[int, Sequence[int]] = 0) -> List[int]:
+              top_logprobs: Union[int, Sequence[int]] = 0,
+              format: Union[None, str, Sequence[Optional[str]]] = None) -> List[int]:
         """``logprobs`` / ``top_logprobs`` per request (or one value for all) as ``DecodeEngine.generate``: rows that
-        ask and rows that do not decode together (``logprobs(row)`` reads a row's)."""
+        ask and rows that do not decode together (``logprobs(row)`` reads a row's).  ``format`` likewise ("json" per
+        request, or the option key ``"format"``): a JSON-mode row's automaton state starts fresh here and moves with
+        the row (``json_state(row)`` reads how it stands)."""
         from .. import ops
 
         eng = self.eng
@@ -1296,6 +1466,12 @@ class ContinuousBatch:
         want = _want_logprobs(logprobs, top_logprobs, k)
         if eng.speculative and any(w >= 0 for w in want):
             raise ValueError("logprobs cannot be combined with speculative decoding")
+        fmt = _want_format(format, list(options), k)
+        if eng.speculative and any(fmt):
+            raise ValueError("format cannot be combined with speculative decoding (the K + 1 expanded rows would "
+                             "each need the state after their drafts)")
+        if any(fmt):
+            eng._json_vocab()
         if k > len(self.free_slots):
             raise ValueError(f"{k} requests but only {len(self.free_slots)} free rows")
         ids = [eng.encode(p) or [eng.cfg.bos_id] for p in prompts]
@@ -1345,7 +1521,10 @@ class ContinuousBatch:
                 eng._lp_bufs()["topn"][sl].copy_(torch.tensor(want, dtype=torch.int32))
             if eng.speculative:
                 eng._spec_begin(rows, slots, ids)
+            if eng._gr is not None or any(fmt):
+                eng._gr_begin(sl, fmt)
         self.want += want
+        self.fmt += fmt
         self.n += k
         self.row_slot += slots
         self.emitted += [0] * k
@@ -1371,8 +1550,9 @@ class ContinuousBatch:
             self._steps[i] += steps
         with_lp = any(w >= 0 for w in self.want)  # some live row wants logprobs: the graphs that compute them
         # speculative engines: each step drafts (n-gram lookup), verifies K + 1 rows per live row and commits
+        with_gr = any(self.fmt)  # some live row is in JSON mode: the graphs with the mask and the advance
         graph = (lambda n: eng._graph_spec(self.n, n, 0)) if eng.speculative else \
-            (lambda n: eng._graph(self.n, n, with_lp))
+            (lambda n: eng._graph(self.n, n, with_lp, with_gr) if with_gr else eng._graph(self.n, n, with_lp))
         with torch.cuda.stream(eng.stream):
             k = eng.steps_per_graph
             if steps >= k:
@@ -1392,6 +1572,14 @@ class ContinuousBatch:
             return None
         with torch.cuda.stream(self.eng.stream):
             return self.eng._spec_stats(row)
+
+    def json_state(self, row: int) -> Optional[str]:
+        """How a live JSON-mode row's document stands ("done", "open", "fail": ``GenResult.json_state``); None for a
+        row that is not in the mode."""
+        if not self.fmt[row]:
+            return None
+        with torch.cuda.stream(self.eng.stream):
+            return self.eng._gr_states(row + 1, [False] * row + [True])[row]
 
     def logprobs(self, row: int, lo: int = 0, hi: Optional[int] = None):
         """``(logprobs, top_logprobs)`` of tokens ``lo .. hi - 1`` (default: all polled so far) of a live row that
@@ -1469,6 +1657,9 @@ class ContinuousBatch:
                 if eng._lp is not None:
                     for key in ("topn", "lp", "top_id", "top_lp"):
                         eng._lp[key][dst] = eng._lp[key][src]
+                if eng._gr is not None:
+                    for key in ("gram_on", "gstate"):
+                        eng._gr[key][dst] = eng._gr[key][src]
                 if eng._spec is not None:  # (the records are per slot and stay)
                     for key in ("given", "drafted", "accepted", "n_step", "step_tokens"):
                         eng._spec[key][dst] = eng._spec[key][src]
@@ -1477,6 +1668,8 @@ class ContinuousBatch:
                     lst[h] = lst[j]
         with torch.cuda.stream(eng.stream):
             eng.rows["slot"][n_new: self.n].fill_(-1)  # vacated rows: skipped by the sampler
+            if eng._gr is not None:
+                eng._gr["gram_on"][n_new: self.n].zero_()
         self.n = n_new
         for lst in self._row_lists():
             del lst[n_new:]

@@ -25,6 +25,8 @@ op                     source                      replaces (Ollama/llama.cpp)
 ``kv_copy_prefix``     csrc/kv_prefix.hip          a slot's cached prompt prefix copied to another slot
 ``sample``             csrc/sample.hip             repeat-penalty/temperature/top-k/top-p
 ``logprob_rows``       csrc/logprob.hip            log-softmax, top-n and token logprobs on device
+``json_mask``          csrc/grammar.hip            format "json": the JSON grammar as a logit mask on device
+``json_advance``       csrc/grammar.hip            the rows' automaton states over the sampled tokens
 ``spec_draft``         csrc/spec.hip               n-gram / given drafts -> K + 1 expanded rows per sequence
 ``spec_accept``        csrc/spec.hip               commit the longest correct draft prefix (lookup decoding)
 ``Plan``               csrc/runtime.hip            per-step schedule + hipGraph replay
@@ -891,6 +893,88 @@ def logprob_chosen(logits: torch.Tensor, V: int, gen: torch.Tensor, keep, lp: to
     assert lp.stride(0) == gen.stride(0) and lp.dtype == torch.float32
     return int(lib.cain_logprob_chosen(_p(logits), logits.stride(0), int(V), logits.shape[0], _p(gen), gen.stride(0),
                                        _p(keep), _p(lp), _stream()))
+
+
+# ------------------------------------------------------------ JSON mode (csrc/grammar.hip, csrc/json_pda.h)
+JSON_STATE_BYTES = 16  # sizeof(JsonState): control word, depth word, 64-bit bracket-kind stack
+JSON_VOCAB_MAX = 1 << 23  # a masked logit carries its token id in the mantissa
+
+
+class CainGrammar(ctypes.Structure):  # csrc/runtime.hip CainGrammar
+    _fields_ = [("gram_on", vp), ("gstate", vp), ("piece_off", vp), ("piece_bytes", vp)]
+
+
+def load_grammar() -> ctypes.CDLL:
+    """``load()`` with JSON mode's entry points' signatures set (a library without them: AttributeError)."""
+    lib = load()
+    if not getattr(lib, "_cain_grammar_sig", False):
+        lib.cain_json_mask.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        lib.cain_json_advance.argtypes = [ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        lib.cain_plan_forward_gr.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp]
+        lib.cain_plan_capture_gr.restype = vp
+        lib.cain_plan_capture_gr.argtypes = [vp, ci, vp, ci, vp, vp, vp, ctypes.POINTER(ci)]
+        if int(lib.cain_json_state_size()) != JSON_STATE_BYTES or \
+                int(lib.cain_grammar_size()) != ctypes.sizeof(CainGrammar):
+            raise NativeOpsUnavailable(f"{LIB_PATH}: JSON-mode records differ from this package's: rebuild "
+                                       f"(python -m cain_amd.build)")
+        lib._cain_grammar_sig = True
+    return lib
+
+
+def json_table(pieces, device) -> dict:
+    """The vocabulary of JSON mode on the device: ``pieces[t]`` is the bytes token ``t`` appends (empty: a special
+    token, never allowed).  Returns ``dict(V, piece_off [V + 1] int32, piece_bytes uint8)``."""
+    from ..engine.jsonmode import piece_table
+
+    if len(pieces) > JSON_VOCAB_MAX:
+        raise ValueError(f"JSON mode supports vocabularies up to {JSON_VOCAB_MAX} tokens, got {len(pieces)}")
+    off, flat = piece_table(pieces)
+    return dict(V=len(pieces), piece_off=torch.from_numpy(off).to(device), piece_bytes=torch.from_numpy(flat).to(device))
+
+
+def json_states(states, device) -> torch.Tensor:
+    """``[(ctrl, depth, stack)]`` (engine/jsonmode.py states) as the device's ``[M, 4]`` int32 JsonState rows."""
+    import numpy as np
+
+    a = np.zeros((len(states), 2), dtype=np.uint64)
+    for i, (c, d, st) in enumerate(states):
+        a[i, 0] = (int(d) << 32) | int(c)
+        a[i, 1] = int(st)
+    return torch.from_numpy(a.view(np.int32).reshape(len(states), 4).copy()).to(device)
+
+
+def json_states_host(gstate: torch.Tensor) -> list:
+    """The inverse of ``json_states``."""
+    import numpy as np
+
+    a = np.ascontiguousarray(gstate.detach().cpu().numpy()).view(np.uint64).reshape(-1, 2)
+    return [(int(x) & 0xFFFFFFFF, int(x) >> 32, int(y)) for x, y in a]
+
+
+def json_mask(logits: torch.Tensor, V: int, gram_on, done, gstate, table: dict, cmax=None) -> int:
+    """BEFORE the sampler: in every row m of fp32 ``logits [M, ldl]`` with ``gram_on[m] != 0`` and ``done[m] == 0``,
+    each token whose bytes cannot continue the row's JSON document from ``gstate[m]`` gets the logit
+    ``-(2^100 (1 + t / 2^23))``; accepted tokens and other rows are not written.  ``cmax [M, V / 16]``: the rows'
+    16-column chunk maxima, rewritten from the masked logits.  Returns the entry's code (non-zero: refused)."""
+    lib = load_grammar()
+    _gpu(logits, gram_on, done, gstate, table["piece_off"], table["piece_bytes"], cmax)
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and gstate.is_contiguous()
+    assert gram_on.dtype == torch.int32 and done.dtype == torch.int32 and int(V) <= table["V"]
+    assert cmax is None or (cmax.dtype == torch.float32 and cmax.is_contiguous() and cmax.shape[1] * 16 == int(V))
+    return int(lib.cain_json_mask(_p(logits), logits.stride(0), int(V), logits.shape[0], _p(gram_on), _p(done),
+                                  _p(gstate), _p(table["piece_off"]), _p(table["piece_bytes"]), _p(cmax), _stream()))
+
+
+def json_advance(gram_on, gen: torch.Tensor, n_gen, done, gstate, table: dict) -> int:
+    """AFTER the sampler: every JSON-mode row that generated a token this step consumes it (``gen[m, n_gen[m] - 1]``);
+    a closed top-level object sets ``done[m]``, an invalid token is taken back (``n_gen[m] -= 1``), fails the state
+    and sets ``done[m]``."""
+    lib = load_grammar()
+    _gpu(gram_on, gen, n_gen, done, gstate)
+    assert gen.dtype == torch.int32 and gen.stride(1) == 1 and gstate.is_contiguous()
+    return int(lib.cain_json_advance(gen.shape[0], int(table["V"]), _p(gram_on), _p(gen), gen.stride(0), _p(n_gen),
+                                     _p(done), _p(gstate), _p(table["piece_off"]), _p(table["piece_bytes"]),
+                                     _stream()))
 
 
 _SAMPLE_WS: dict = {}

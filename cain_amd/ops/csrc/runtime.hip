@@ -127,6 +127,16 @@ struct CainLogprob {
   const int* target;  // teacher forcing
 };
 
+// JSON mode of a decode forward (grammar.hip; cain_plan_forward_gr / cain_plan_capture_gr): the mask runs between the
+// LM head (after cain_logprob_pre: logprobs stay the model's own distribution) and the sampler, the state advances
+// after it.
+struct CainGrammar {
+  const int* gram_on;          // per row: 0 off, else the row is in JSON mode
+  void* gstate;                // per row: 16 bytes of JsonState (json_pda.h)
+  const int* piece_off;        // [V + 1]: token t's bytes are piece_bytes[piece_off[t] .. piece_off[t + 1])
+  const uint8_t* piece_bytes;
+};
+
 }  // extern "C"
 
 namespace {
@@ -172,8 +182,9 @@ int max_rows(const CainPlanDesc& d) {
 // 5 launches per layer: QKV(+RMSNorm, bias, RoPE, KV append) -> attention(+combine) ->
 // O(+residual) -> gate/up(+RMSNorm, act*mul) -> down(+residual); 6 in a layer whose V rows are Q6_K beside Q4 q / k.
 // lq: the caller's logprob buffers (null: none -- the launches are exactly those of a plan without the feature)
+// gr: JSON mode's buffers (null: none, likewise)
 int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_sample, hipStream_t st,
-            const CainLogprob* lq = nullptr) {
+            const CainLogprob* lq = nullptr, const CainGrammar* gr = nullptr) {
   const CainPlanDesc& d = p.d;
   const int qkv_dim = (d.H + 2 * d.Hkv) * d.hd;
   const int q_dim = d.H * d.hd;
@@ -268,6 +279,9 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
   if (lq && !want_sample)
     CK(cain_logprob_rows(d.logits, d.V, d.V, M, r.slot, nullptr, lq->topn, lq->nmax, lq->target, nullptr, lq->lp,
                          lq->top_id, lq->top_lp, st));
+  if (gr)  // the chunk maxima the LM head wrote are rewritten from the masked logits (a sampler starts from them)
+    CK(cain_json_mask(d.logits, d.V, d.V, M, gr->gram_on, r.done, gr->gstate, gr->piece_off, gr->piece_bytes,
+                      cm ? p.cmax : nullptr, st));
   if (want_sample) {
     // the chunk-max sampler refuses (< 0) vocabularies beyond its chunk capacity: the two-stage / one-workgroup
     // kernels take those
@@ -282,6 +296,9 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
       CK(cain_sample_ex(d.logits, d.V, d.V, r.tok, r.pos, r.gen, r.ldg, r.n_gen, r.max_new, r.done, r.hist, r.slot,
                         d.T_max, M, r.sample_params, p.sample_ws, p.sample_ws_bytes, st));
     if (lq) CK(cain_logprob_chosen(d.logits, d.V, d.V, M, r.gen, r.ldg, lq->keep, lq->lp, st));
+    if (gr)
+      CK(cain_json_advance(M, d.V, gr->gram_on, r.gen, r.ldg, r.n_gen, r.done, gr->gstate, gr->piece_off,
+                           gr->piece_bytes, st));
   }
   return 0;
 }
@@ -298,6 +315,16 @@ int forward_spec(const Plan& p, int R, const CainRows& r, const CainSpec& s, hip
   CK(cain_spec_accept(&s, R, T, r.tok, r.pos, r.slot, r.n_gen, r.max_new, r.done, r.hist, r.gen, r.ldg,
                       r.sample_params, st));
   return 0;
+}
+
+// What the _gr entries refuse before anything is launched: logprobs without logits; JSON mode on anything but a
+// decode forward (logits, sampler and the rows' sampling state), or with a table or state missing.
+bool gr_args_ok(const CainRows* r, int want_logits, int want_sample, const CainLogprob* lq, const CainGrammar* gr) {
+  if (!r || (lq && !want_logits)) return false;
+  if (lq && (!lq->topn || (want_sample && (!lq->keep || !lq->lp || !lq->top_id || !lq->top_lp)))) return false;
+  if (!gr) return true;
+  if (!want_logits || !want_sample || !r->n_gen || !r->done || !r->gen || r->ldg < 1) return false;
+  return gr->gram_on && gr->gstate && gr->piece_off && gr->piece_bytes;
 }
 
 bool spec_rows_ok(const Plan& p, int R, const CainRows* r, const CainSpec* s) {
@@ -355,13 +382,24 @@ CAIN_API int cain_plan_forward_lp(void* plan, int M, const CainRows* rows, int w
   return forward(*p, M, *rows, want_logits, want_sample, st, lq);
 }
 
+// The decode forward under JSON mode (CainGrammar), with token log-probabilities when `lq` is given too: needs
+// want_logits and want_sample (refused before any launch otherwise); a null `gr` runs what cain_plan_forward_lp runs.
+CAIN_API int cain_plan_forward_gr(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
+                                  const CainLogprob* lq, const CainGrammar* gr, hipStream_t st) {
+  auto* p = static_cast<Plan*>(plan);
+  g_fail[0] = 0;
+  if (M < 1 || M > max_rows(p->d) || !gr_args_ok(rows, want_logits, want_sample, lq, gr)) return -1;
+  return forward(*p, M, *rows, want_logits, want_sample, st, lq, gr);
+}
+
 // Record `steps` decode steps over M rows into a graph; returns the executable graph (or null).  Each step with its
-// token log-probabilities when `lq` is given (null: the graph of cain_plan_capture, launch for launch).
-CAIN_API void* cain_plan_capture_lp(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
-                                    hipStream_t st, int* err) {
+// token log-probabilities when `lq` is given and under JSON mode when `gr` is (both null: the graph of
+// cain_plan_capture, launch for launch).
+CAIN_API void* cain_plan_capture_gr(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
+                                    const CainGrammar* gr, hipStream_t st, int* err) {
   auto* p = static_cast<Plan*>(plan);
   *err = 0;
-  if (M < 1 || M > max_rows(p->d) || steps < 1) {
+  if (M < 1 || M > max_rows(p->d) || steps < 1 || !gr_args_ok(rows, 1, 1, lq, gr)) {
     *err = -1;
     return nullptr;
   }
@@ -372,7 +410,7 @@ CAIN_API void* cain_plan_capture_lp(void* plan, int M, const CainRows* rows, int
     return nullptr;
   }
   int fe = 0;
-  for (int s = 0; s < steps && fe == 0; ++s) fe = forward(*p, M, *rows, 1, 1, st, lq);
+  for (int s = 0; s < steps && fe == 0; ++s) fe = forward(*p, M, *rows, 1, 1, st, lq, gr);
   e = hipStreamEndCapture(st, &g);
   if (fe != 0 || e != hipSuccess) {
     *err = fe ? fe : int(e);
@@ -387,6 +425,11 @@ CAIN_API void* cain_plan_capture_lp(void* plan, int M, const CainRows* rows, int
     return nullptr;
   }
   return ex;
+}
+
+CAIN_API void* cain_plan_capture_lp(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
+                                    hipStream_t st, int* err) {
+  return cain_plan_capture_gr(plan, M, rows, steps, lq, nullptr, st, err);
 }
 
 CAIN_API void* cain_plan_capture(void* plan, int M, const CainRows* rows, int steps, hipStream_t st, int* err) {
@@ -492,6 +535,7 @@ CAIN_API int cain_stream_destroy(void* st) { return hipStreamDestroy(static_cast
 
 CAIN_API int cain_rows_size() { return int(sizeof(CainRows)); }
 CAIN_API int cain_logprob_size() { return int(sizeof(CainLogprob)); }
+CAIN_API int cain_grammar_size() { return int(sizeof(CainGrammar)); }
 CAIN_API int cain_plan_desc_size() { return int(sizeof(CainPlanDesc)); }
 CAIN_API int cain_layer_size() { return int(sizeof(CainLayer)); }
 

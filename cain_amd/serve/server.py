@@ -39,6 +39,13 @@ logprob is the natural-log softmax of the model's own logits: temperature 1, bef
 top-p; the alternatives are the n most likely tokens of that distribution.  ``id`` (the token id) is this server's
 addition: random-weight vocabularies detokenise badly.  Requests that do not ask get exactly the keys they always got.
 
+JSON mode: ``"format": "json"`` on ``/api/generate`` and ``/api/chat`` constrains the generated tokens to an RFC 8259
+document whose top-level value is an object (engine/jsonmode.py; on the HIP backend a logit mask inside the decode
+graphs, csrc/grammar.hip).  The row ends on the brace that closes the object (``done_reason: "stop"``); a row whose
+``num_predict`` runs out first returns a prefix that can still be completed (``"length"``).  Absent or ``""``: free
+text, exactly as before.  A JSON schema object or any other value is a 400; so is ``format`` on a ``--speculative``
+server, and on a model whose vocabulary cannot spell JSON (the synthetic tokenizer of the random-init tags).
+
 Tracing: started with ``--trace-dir DIR``, the engine backend records every decode batch
 with ``torch.profiler`` (host ops + GPU kernels) and writes a Chrome trace to DIR; the response JSON
 names it in ``cain_trace`` so the client can file it with its run (the study moves it into run_dir).
@@ -96,6 +103,7 @@ class Job:
     logprobs: bool = False           # the response carries ``logprobs`` (one entry per generated token)
     top_logprobs: int = 0            # alternatives per entry (0 .. 20)
     lp_entries: List[Dict[str, Any]] = field(default_factory=list)  # the entries produced so far
+    format: Optional[str] = None     # "json": Ollama's JSON mode (engine/jsonmode.py)
 
 
 def logprob_entries(tok, ids, lps, tops) -> List[Dict[str, Any]]:
@@ -130,6 +138,10 @@ class Backend:
 
     def model_info(self, model: str) -> Dict[str, Any]:
         return {}
+
+    def check_format(self, model: str, fmt: str) -> None:
+        """Raise ValueError when this backend cannot serve ``format: fmt`` for ``model`` (default: the field is
+        accepted and ignored, as a backend without a model does)."""
 
     def vocab_size(self, model: str) -> Optional[int]:
         """Token ids a request's ``context`` may hold are below this (None: not checked)."""
@@ -266,11 +278,31 @@ class EngineBackend(Backend):
                                                if tok.tok.id_to_token(i) is not None)
         return out
 
+    def check_format(self, model: str, fmt: str) -> None:
+        if self.speculative:
+            raise ValueError("format cannot be combined with speculative decoding (--speculative)")
+        # ValueError: the model's vocabulary cannot spell JSON.  An engine that is loaded answers for its own vocabulary
+        # (set_json_vocab included) and a checkpoint's engine is loaded here, as prompt_for does; a random-init tag that
+        # is not loaded yet keeps its lazy load in the scheduler thread: its synthetic tokenizer is judged on its own.
+        from ..models.hf import checkpoint_for
+
+        with self._lock:
+            eng = self.engines.get(model)
+        if eng is None and model in self._models and not checkpoint_for(model):
+            from ..engine import jsonmode
+            from ..models.config import get_config
+            from ..models.tokenizer import get_tokenizer
+
+            cfg = get_config(model)
+            jsonmode.check_vocabulary(jsonmode.token_bytes(get_tokenizer(cfg), cfg.vocab))
+            return
+        self.engine(model)._json_vocab()
+
     def run(self, model: str, jobs: List[Job]) -> None:
         eng = self.engine(model)
         tok = eng.tokenizer
         streams = [j.stream for j in jobs]
-        decs = [StreamDecoder(tok) for _ in jobs]
+        decs = [StreamDecoder(eng.text_decoder(bool(j.format))) for j in jobs]
 
         def on_tokens(new_per_row: List[List[int]], lps=None) -> None:
             for r, (j, d, ids) in enumerate(zip(jobs, decs, new_per_row)):
@@ -286,6 +318,8 @@ class EngineBackend(Backend):
         def gen():
             kw = dict(logprobs=[j.logprobs for j in jobs], top_logprobs=[j.top_logprobs for j in jobs]) \
                 if any(j.logprobs for j in jobs) else {}
+            if any(j.format for j in jobs):
+                kw["format"] = [j.format for j in jobs]
             return eng.generate([j.prompt for j in jobs], [j.num_predict for j in jobs], [j.options for j in jobs],
                                 on_tokens=on_tokens if any(streams) else None,
                                 context=[j.context for j in jobs] if any(j.context for j in jobs) else None, **kw)
@@ -365,14 +399,16 @@ class EngineBackend(Backend):
         if ok:
             t0 = time.perf_counter_ns()
             rows = cb.admit(ids, [j.num_predict for j in ok], [j.options for j in ok],
-                            [j.logprobs for j in ok], [j.top_logprobs for j in ok])
+                            [j.logprobs for j in ok], [j.top_logprobs for j in ok],
+                            **({"format": [j.format for j in ok]} if any(j.format for j in ok) else {}))
             eng.stream.synchronize()
             t_pre = time.perf_counter_ns()
             cb.step(1)  # the new rows' first token on its own (the live rows advance one step with them)
             eng.stream.synchronize()
             t_first = time.perf_counter_ns()
             for r, j in zip(rows, ok):
-                live[r] = {"job": j, "t0": t0, "t_pre": t_pre, "t_first": t_first, "dec": StreamDecoder(tok)}
+                live[r] = {"job": j, "t0": t0, "t_pre": t_pre, "t_first": t_first,
+                           "dec": StreamDecoder(eng.text_decoder(bool(j.format)))}
         cb.step()
         new, fin = cb.poll()
         now = time.perf_counter_ns()
@@ -394,8 +430,10 @@ class EngineBackend(Backend):
                 tail = st["dec"].flush()
                 if tail:
                     j.stream(tail)
-            reason = "stop" if _stopped(toks, cb.options[r]) else "length"
-            j.result = GenResult(model, list(cb.prompt_tokens[r]), toks, tok.decode(toks), reason,
+            js = cb.json_state(r)  # JSON mode: the row ended on the brace that closes its object
+            reason = "stop" if _stopped(toks, cb.options[r]) or js == "done" else "length"
+            j.result = GenResult(model, list(cb.prompt_tokens[r]), toks,
+                                 eng.text_decoder(js is not None).decode(toks), reason, json_state=js,
                                  load_duration_ns=0, prompt_eval_duration_ns=int(st["t_pre"] - st["t0"]),
                                  eval_duration_ns=int(now - st["t_pre"]),
                                  total_duration_ns=int(now - j.t_submit * 1e9), prompt_cached=int(cb.reused[r]),
@@ -649,7 +687,26 @@ class OllamaHandler(BaseHTTPRequestHandler):
         if want_lp and getattr(self.scheduler.backend, "speculative", 0):
             return self._send_json(400, {"error": "logprobs cannot be combined with speculative decoding "
                                                   "(--speculative)"})
+        # Ollama's format: absent or "" -- free text; "json" -- JSON mode; a JSON schema (an object) is not supported
+        # (the engine's per-row option key "format" counts as the field: it gets the same checks and travels as the
+        # job's format, not inside the sampling options)
         opts = dict(body.get("options") or {})
+        opt_fmt = opts.pop("format", None)
+        fmt = body.get("format")
+        if fmt in (None, ""):
+            fmt = opt_fmt
+        if isinstance(fmt, dict):
+            return self._send_json(400, {"error": 'format: JSON schema is not supported, only "json"'})
+        if fmt not in (None, "", "json"):
+            return self._send_json(400, {"error": 'format must be "json" or absent'})
+        fmt = fmt or None
+        if fmt:
+            try:
+                self.scheduler.backend.check_format(model, fmt)
+            except KeyError as exc:
+                return self._send_json(404, {"error": str(exc).strip("'\"")})
+            except ValueError as exc:
+                return self._send_json(400, {"error": str(exc)})
         n = opts.get("num_predict")
         # the length policy reads the user's words ("In N words ..."), not the template around them
         num_predict = int(n) if n is not None and int(n) > 0 else default_num_predict(text)
@@ -659,7 +716,7 @@ class OllamaHandler(BaseHTTPRequestHandler):
         job = Job(model, prompt, num_predict, opts, stream=chunks.put if stream else None, context=context,
                   want_context=not chat and (context is not None or bool(getattr(self.scheduler.backend,
                                                                                 "prefix_cache", False))),
-                  logprobs=want_lp, top_logprobs=n_top)
+                  logprobs=want_lp, top_logprobs=n_top, format=fmt)
         try:
             self.scheduler.submit(job)
         except KeyError as exc:
@@ -818,12 +875,19 @@ def generate_main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16")
     ap.add_argument("--checkpoint", metavar="PATH", help="a Hugging Face checkpoint directory, served as --model")
     ap.add_argument("--speculative", type=int, default=0, metavar="K", help="speculative decoding with K n-gram drafts")
+    ap.add_argument("--format", choices=["json"], default=None,
+                    help="json: constrain the output to a JSON object (Ollama's format: \"json\")")
     ns = ap.parse_args(argv)
     if ns.checkpoint:
         register_checkpoints([f"{ns.model}={ns.checkpoint}"])
     be = EngineBackend([ns.model], device=ns.device, max_batch=1, weight_dtype=ns.weights, kv_dtype=ns.kv,
                        speculative=ns.speculative)
     opts = {k: v for k, v in (("temperature", ns.temperature), ("seed", ns.seed)) if v is not None}
-    job = Job(ns.model, ns.prompt, ns.num_predict or default_num_predict(ns.prompt), opts)
+    job = Job(ns.model, ns.prompt, ns.num_predict or default_num_predict(ns.prompt), opts, format=ns.format)
+    if ns.format:
+        try:
+            be.check_format(ns.model, ns.format)
+        except ValueError as exc:
+            raise SystemExit(f"--format {ns.format}: {exc}")
     be.run(ns.model, [job])
     print(json.dumps(_result_json(job)))
