@@ -42,7 +42,7 @@ from ..models.config import ModelConfig, get_config, rope_inv_freq
 from ..models.hf import checkpoint_for, load_hf_weights, load_pretrained, load_tokenizer
 from ..models.tokenizer import get_tokenizer
 from . import jsonmode
-from .speculative import K_MAX, SeqState
+from .speculative import K_MAX, SeqState, draft_model_given, draft_model_rows, draft_token, dvalid_after
 from .speculative import draft as spec_draft_host
 from ..models.weights import WEIGHT_DTYPES, ModelWeights, pack_for_engine, random_weights, roundtrip_weights
 
@@ -399,7 +399,8 @@ class DecodeEngine:
                  max_batch: int = 16, max_context: int = 2048, seed: int = 0, backend: Optional[str] = None,
                  steps_per_graph: int = 8, weights: Optional[ModelWeights] = None, tokenizer=None,
                  keep_natural: bool = False, weight_dtype: str = "bf16", kv_dtype: str = "bf16", cu_limit: int = 0,
-                 prefix_cache: Optional[bool] = None, speculative: Optional[int] = None):
+                 prefix_cache: Optional[bool] = None, speculative: Optional[int] = None,
+                 draft_model: Union[None, str, ModelWeights] = None, draft_weight_dtype: Optional[str] = None):
         """``weight_dtype="fp8"``: GEMM weights quantised per row to e4m3 (half the weight bytes per decode step):
         forwards of up to 16 rows run W8A16 (gemm_w8.hip, bf16 activations), wider ones W8A8 (wgemm8.hip: the
         activations quantised per row to e4m3, fp8 MFMA) up to 256 rows; CAIN_W8A8=0 keeps W8A16 only (<= 64
@@ -433,7 +434,14 @@ class DecodeEngine:
         draft is kept only when it is the token the sampler draws, so drafts change the number of steps, not the
         tokens (a K + 1-row forward rounds differently from a 1-row one: against a plain engine, equal up to near-ties).  0 (default; None: ``CAIN_SPECULATIVE``): off, nothing changes.  A
         batch then holds at most ``rows per forward // (K + 1)`` sequences; not together with ``prefix_cache`` or
-        ``logprobs``."""
+        ``logprobs``.
+        ``draft_model`` (needs ``speculative > 0``; None: ``CAIN_DRAFT_MODEL``): a smaller model with the same
+        tokenizer -- a tag, a checkpoint path or ``ModelWeights`` -- proposes each step's K drafts instead of the
+        n-gram lookup (engine/speculative.py "Draft model"): an inner engine ``self.draft`` on this engine's device
+        and stream with its own weights (``draft_weight_dtype``, default ``weight_dtype``), plan and KV cache, run
+        inside the same decode graphs (csrc/runtime.hip forward_spec_model).  The first draft forward has two rows
+        per sequence, so a batch holds at most 32 sequences (64 rows: what every weight format's forward takes).
+        The tokens stay those of the engine without a draft model; what changes is how many drafts are accepted."""
         self.cfg = get_config(model) if isinstance(model, str) else model
         self._json_pieces: Optional[List[bytes]] = None  # JSON mode's vocabulary, made at first use (_json_vocab)
         self._json_lock = threading.Lock()
@@ -461,6 +469,12 @@ class DecodeEngine:
         if self.speculative and self.prefix_cache:
             raise ValueError("speculative decoding and prefix_cache cannot be combined (the slot records assume one "
                              "token per step)")
+        if draft_model is None and self.speculative:  # (the environment names the draft of speculative engines only)
+            draft_model = os.environ.get("CAIN_DRAFT_MODEL") or None
+        if draft_model is not None and not self.speculative:
+            raise ValueError("draft_model needs speculative > 0")
+        self.draft: Optional["DecodeEngine"] = None  # the draft model's inner engine (speculative.py "Draft model")
+        self._specd: Optional[Dict] = None  # its device buffers (hip backend), made at first use (_spec_draft_bufs)
         self.prefill_rows_total = 0  # rows fed to prefill forwards so far
         if self.cu_limit and (self.cu_limit < 0 or self.cu_limit % 8):
             raise ValueError(f"cu_limit must be a positive multiple of 8 (or 0), got {cu_limit}")
@@ -479,6 +493,8 @@ class DecodeEngine:
         self.row_cap = int(row_cap)
         # speculative: a forward verifies K + 1 rows per sequence, so fewer sequences fit the rows of one forward
         self.max_batch = int(max(1, min(max_batch, row_cap // (self.speculative + 1))))
+        if draft_model is not None:  # the draft model's first forward: 2 rows per sequence, whatever its format
+            self.max_batch = min(self.max_batch, W8_MAX_ROWS // 2)
         # prompt tokens per prefill forward: the engine's own row count when that is wider (a 256-row engine
         # prefills 256 tokens per forward on the wide GEMM: half the launches of 128-row chunks)
         self.prefill_chunk = int(min(int(os.environ.get("CAIN_PREFILL_ROWS", "0") or 0)
@@ -506,6 +522,8 @@ class DecodeEngine:
             self.ref = ReferenceModel(ref_w, memo_weights=self.device.type == "cpu", kv_dtype=kv_dtype)
         else:
             raise ValueError(f"unknown backend {backend!r}")
+        if draft_model is not None:
+            self._init_draft(draft_model, draft_weight_dtype or weight_dtype)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         self.load_duration_ns = time.perf_counter_ns() - t0
@@ -513,6 +531,47 @@ class DecodeEngine:
         self.last_ttft_ns = 0
         # per cache slot: the tokens whose KV the slot holds at positions 0 .. len - 1 (prefix_cache; else unused)
         self.slot_tokens: List[List[int]] = [[] for _ in range(self.max_batch)]
+
+    def _init_draft(self, draft_model, weight_dtype: str) -> None:
+        """The draft model's inner engine: the target's cache slots, ``T_max``, device and stream, no speculation of
+        its own.  ``draft_model``: ``ModelWeights``, a checkpoint path or a tag (``CAIN_CHECKPOINTS`` resolves it as
+        it does the target's)."""
+        from ..models.hf import checkpoint_config
+        from ..models.tokenizer import SyntheticTokenizer
+
+        is_path = isinstance(draft_model, str) and os.path.exists(draft_model)
+        cfg = draft_model.cfg if isinstance(draft_model, ModelWeights) else \
+            checkpoint_config(draft_model) if is_path else get_config(draft_model)
+        if cfg.max_context < self.T_max:
+            raise ValueError(f"draft model {cfg.name}: max_context {cfg.max_context} is below the engine's context "
+                             f"({self.T_max})")
+        kw = dict(device=self.device, max_batch=self.max_batch, max_context=self.T_max, seed=self.seed,
+                  backend=self.backend, steps_per_graph=self.steps_per_graph, keep_natural=self.keep_natural,
+                  weight_dtype=weight_dtype, kv_dtype=self.kv_dtype, prefix_cache=False, speculative=0)
+        if isinstance(draft_model, ModelWeights):
+            d = DecodeEngine(cfg, weights=draft_model, **kw)
+        elif is_path:
+            d = DecodeEngine.from_pretrained(draft_model, **kw)
+        else:
+            d = DecodeEngine(draft_model, **kw)
+        a, b = self.tokenizer, d.tokenizer
+        if not isinstance(a, SyntheticTokenizer) and not isinstance(b, SyntheticTokenizer):
+            for t in range(min(self.cfg.vocab, d.cfg.vocab)):
+                if a.piece(t) != b.piece(t):
+                    d.close()
+                    raise ValueError(f"draft model {d.cfg.name}: token {t} is {b.piece(t)!r}, the target's is "
+                                     f"{a.piece(t)!r} (a draft model needs the target's tokenizer)")
+        if d.T_max != self.T_max or d.max_batch != self.max_batch:
+            d.close()
+            raise ValueError(f"draft model {d.cfg.name}: {d.max_batch} slots of {d.T_max} positions, the engine has "
+                             f"{self.max_batch} of {self.T_max}")
+        if self.backend == "hip":
+            if 2 * self.max_batch > min(d.rows["tok"].shape[0], d.row_cap):
+                d.close()
+                raise ValueError(f"draft model {d.cfg.name}: its forwards take {d.rows['tok'].shape[0]} rows, the "
+                                 f"first draft forward needs {2 * self.max_batch}")
+            d.stream, d.cu_limit = self.stream, self.cu_limit  # one stream: the draft forwards sit in the same graphs
+        self.draft = d
 
     # ---------------------------------------------------------------- hip setup
     def _init_hip(self) -> None:
@@ -856,6 +915,30 @@ class DecodeEngine:
         b["given"][ri] = giv.to(self.device)
         for k in ("drafted", "accepted", "n_step"):
             b[k][ri] = 0
+        if self.draft is not None:  # the draft cache of each slot: prompt[:-1], as the target's prefill
+            dm = self.draft
+            dm._forget_slots(slots)
+            dm._prefill([[draft_token(t, dm.cfg.vocab, dm.cfg.bos_id) for t in p] for p in ids], list(slots))
+            self._spec_draft_bufs()["dvalid"][torch.tensor(list(slots), dtype=torch.long, device=self.device)] = \
+                torch.tensor([len(p) - 1 for p in ids], dtype=torch.int32).to(self.device)
+
+    def _spec_draft_bufs(self) -> Dict:
+        """Device buffers of draft-model mode (csrc/spec.h CainSpecDraft), made when the mode first runs."""
+        if self._specd is None:
+            from .. import ops
+
+            self._specd = ops.spec_draft_alloc(self._spec_bufs(), self.draft.cfg.vocab, self.draft.cfg.bos_id)
+        return self._specd
+
+    def _spec_model_args(self, B: int):
+        """(target plan, draft plan for 2 B rows, draft plan for B rows, rows, CainSpec in given mode, CainSpecDraft)
+        of a draft-model step over ``B`` sequences."""
+        from .. import ops
+
+        vp = ctypes.c_void_p
+        return (vp(self._plan(B * (self.speculative + 1))), vp(self.draft._plan(2 * B)), vp(self.draft._plan(B)),
+                self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), 1),
+                ops.spec_draft_struct(self._spec_draft_bufs()))
 
     def _spec_stats(self, row: int) -> Dict:
         """Counters of decode row ``row``: drafts proposed, drafts accepted, live steps, tokens per step."""
@@ -867,13 +950,22 @@ class DecodeEngine:
     def _forward_spec(self, B: int, mode: int) -> None:
         from .. import ops
 
-        lib = ops.load_spec()
-        rs, sp = self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), mode)
-        plan = self._plan(B * (self.speculative + 1))
+        stream_h = ctypes.c_void_p(self.stream.cuda_stream)
+        if self.draft is not None:
+            lib = ops.load_spec_model()
+            plan, d2, d1, rs, sp, sd = self._spec_model_args(B)
+        else:
+            lib = ops.load_spec()
+            rs, sp = self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), mode)
+            plan = self._plan(B * (self.speculative + 1))
         _set_cu_budget(self.lib, self.cu_limit)
         try:
-            rc = lib.cain_plan_forward_spec(ctypes.c_void_p(plan), B, ctypes.byref(rs), ctypes.byref(sp),
-                                            ctypes.c_void_p(self.stream.cuda_stream))
+            if self.draft is not None:
+                rc = lib.cain_plan_forward_spec_model(plan, d2, d1, B, ctypes.byref(rs), ctypes.byref(sp),
+                                                      ctypes.byref(sd), stream_h)
+            else:
+                rc = lib.cain_plan_forward_spec(ctypes.c_void_p(plan), B, ctypes.byref(rs), ctypes.byref(sp),
+                                                stream_h)
         finally:
             _set_cu_budget(self.lib, 0)
         if rc != 0:
@@ -885,17 +977,26 @@ class DecodeEngine:
         sequences as one graph; cache entries of their own, beside the plain graphs."""
         from .. import ops
 
-        key = (B, steps, "spec", mode)
+        key = (B, steps, "spec", "draft" if self.draft is not None else mode)
         g = self._graphs.get(key)
         if g is None:
-            lib = ops.load_spec()
-            rs, sp = self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), mode)
             err = ctypes.c_int(0)
-            plan = self._plan(B * (self.speculative + 1))
+            stream_h = ctypes.c_void_p(self.stream.cuda_stream)
+            if self.draft is not None:
+                lib = ops.load_spec_model()
+                plan, d2, d1, rs, sp, sd = self._spec_model_args(B)
+            else:
+                lib = ops.load_spec()
+                rs, sp = self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), mode)
+                plan = self._plan(B * (self.speculative + 1))
             _set_cu_budget(self.lib, self.cu_limit)
             try:
-                g = lib.cain_plan_capture_spec(ctypes.c_void_p(plan), B, ctypes.byref(rs), ctypes.byref(sp), steps,
-                                               ctypes.c_void_p(self.stream.cuda_stream), ctypes.byref(err))
+                if self.draft is not None:
+                    g = lib.cain_plan_capture_spec_model(plan, d2, d1, B, ctypes.byref(rs), ctypes.byref(sp),
+                                                         ctypes.byref(sd), steps, stream_h, ctypes.byref(err))
+                else:
+                    g = lib.cain_plan_capture_spec(ctypes.c_void_p(plan), B, ctypes.byref(rs), ctypes.byref(sp),
+                                                   steps, stream_h, ctypes.byref(err))
             finally:
                 _set_cu_budget(self.lib, 0)
             if not g:
@@ -904,6 +1005,8 @@ class DecodeEngine:
         return g
 
     def close(self) -> None:
+        if getattr(self, "draft", None) is not None:
+            self.draft.close()
         lib = getattr(self, "lib", None)
         if lib is None:
             return
@@ -969,6 +1072,8 @@ class DecodeEngine:
             raise ValueError("logprobs cannot be combined with speculative decoding")
         if drafts is not None and not self.speculative:
             raise ValueError("drafts need an engine with speculative > 0")
+        if drafts is not None and self.draft is not None:
+            raise ValueError("drafts cannot be combined with a draft model (the draft model writes the drafts)")
         if drafts is not None and len(drafts) != B:
             raise ValueError(f"{len(drafts)} drafts for {B} prompts")
         if B > self.max_batch:
@@ -1319,7 +1424,8 @@ class DecodeEngine:
         """The oracle backend under the speculative rule (engine/speculative.py): per step the drafts of the host
         rule, one oracle forward over the K + 1 rows, the host sampler per row, the host accept.  The random stream
         is numpy's, one draw per sampled token, so each row samples from the generator state plain decoding has at
-        its generated index and the state is set back to the one after the last committed token."""
+        its generated index and the state is set back to the one after the last committed token.  With a draft model
+        the drafts are its own: its forwards on a cache of its own, sampled from the state the step starts in."""
         t0 = time.perf_counter_ns()
         K, V = self.speculative, self.cfg.vocab
         gens, stats = [], []
@@ -1330,7 +1436,25 @@ class DecodeEngine:
             st = SeqState(tok=p[-1], pos=len(p) - 1, max_new=nps[i], eos_id=o["eos_id"], stop=o["stop"], seq=list(p))
             cache: list = []
             fed = 0  # positions the cache holds
+            dm, dcache, dvalid = self.draft, [], len(p) - 1
+            if dm is not None and len(p) > 1:  # the draft cache: prompt[:-1]
+                dm.ref.forward(torch.tensor([[draft_token(t, dm.cfg.vocab, dm.cfg.bos_id) for t in p[:-1]]],
+                                            device=self.device), cache=dcache)
             while not st.done:
+                pos0, d = st.pos, 0
+                if dm is not None:
+                    # the draft model's forwards, sampled from the generator state the target rows start from
+                    d, catch_up, own = draft_model_rows(st.seq, st.pos, st.n_gen, K, self.T_max, st.max_new, dvalid,
+                                                        dm.cfg.vocab, dm.cfg.bos_id)
+                    state0, dj, feed = rng.bit_generator.state, [], [r[0] for r in (catch_up, own) if r[2] >= 0]
+                    for _ in range(d):
+                        lg = dm.ref.forward(torch.tensor([feed], device=self.device), cache=dcache,
+                                            last_only=True)[0, -1].float().cpu()
+                        dj.append(sample_host(lg, st.gen + dj, o, rng))
+                        feed = [draft_token(dj[-1], dm.cfg.vocab, dm.cfg.bos_id)]
+                    rng.bit_generator.state = state0
+                    given = [-1] * self.T_max
+                    draft_model_given(given, st.n_gen, dj, K)
                 dr = spec_draft_host(st.seq, st.pos, st.n_gen, K, self.T_max, st.max_new,
                                      given=[] if drafts is not None and given is None else given, vocab=V)
                 step = torch.tensor([st.seq[fed: st.pos + 1] + dr], device=self.device)
@@ -1344,6 +1468,10 @@ class DecodeEngine:
                 fed = st.pos
                 for li in range(len(cache)):  # rejected rows leave the cache
                     cache[li] = [cache[li][0][:, :fed], cache[li][1][:, :fed]]
+                if d > 0:
+                    dvalid = dvalid_after(pos0, d, st.pos)
+                    for li in range(len(dcache)):
+                        dcache[li] = [dcache[li][0][:, :dvalid], dcache[li][1][:, :dvalid]]
             gens.append(list(st.gen))
             stats.append(dict(draft_count=st.drafted, draft_accepted=st.accepted, decode_steps=len(st.step_tokens),
                               step_tokens=list(st.step_tokens)))

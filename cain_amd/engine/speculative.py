@@ -33,6 +33,28 @@ Accept
 
 K / V of rejected rows stay in the cache at positions above the sequence's: attention masks by position, so nothing
 reads them, and later tokens overwrite them.
+
+Draft model (a third source of drafts; verify and accept are given mode's, unchanged)
+    A speculative engine may own a second, smaller model: its own weights, plan and KV cache, with the target's
+    number of cache slots and ``T_max``; a sequence uses the same slot in both caches.  ``dvalid[slot]`` counts the
+    leading positions of the slot's draft cache whose K / V belong to the record ``seq``; after a request's prefill
+    (the draft model runs ``prompt[:-1]``, no logits, no sampler) it is ``len(prompt) - 1``.
+    One step, with ``d = clip(K, pos, ng, K, T_max, max_new)`` (0 for a done or masked sequence, and on a sequence's
+    last token: such a sequence runs no draft row and its ``dvalid`` stays):
+    First draft forward, two rows: the catch-up row ``seq[pos - 1]`` at ``pos - 1``, masked unless
+    ``dvalid == pos - 1`` (the step before accepted every draft), which only writes K / V; and the sequence's own row
+    ``seq[pos]`` at ``pos``, on which the ordinary sampler runs with ``n_gen = ng``, the sequence's ring and the
+    request's own options -- stop ids off, no budget.  It draws ``d_1``.
+    Draft forwards ``j = 2 .. K``, one row: ``d_{j-1}`` at ``pos + j - 1`` with ``n_gen = ng + j - 1``, the ring
+    carrying ``d_1 .. d_{j-1}`` as ``draft_ring`` writes them; masked when ``j > d``.  It draws ``d_j``.
+    The sampler's random stream is keyed by (seed, generated index), so the draft row that draws ``d_j`` uses the
+    uniform number of the target row that decides whether ``d_j`` is accepted: equal distributions give equal
+    tokens.  No rejection-sampling arithmetic: a draft is still kept only when it is the token.
+    ``given[ng + j - 1] = d_j`` for ``j <= d``, ``given[ng + d] = -1`` when ``d < K``; then given mode.
+    After accept, with ``pos'`` the sequence's new position: ``dvalid = min(pos + d, pos')`` -- for a sequence that
+    goes on, ``min(pos + d, pos + a + 1)``: the next step needs one row when ``a < d`` and two when ``a == d``.
+    A token id at or above the draft model's vocabulary enters the draft forward as the draft model's ``bos_id``; a
+    draft id at or above the target's ends the draft (given mode's ``vocab`` rule).
 """
 from __future__ import annotations
 
@@ -151,3 +173,47 @@ class SeqState:
         self.accepted += c - 1
         self.step_tokens.append(c)
         return c
+
+
+# ---------------------------------------------------------------------------------------------- draft model
+MASKED_ROW = (0, 0, -1, 0, 0, 0)  # (tok, pos, slot, n_gen, max_new, done) of a row no forward acts on
+
+
+def draft_token(t: int, dvocab: int, dbos: int) -> int:
+    """A token id as the draft model's embedding takes it."""
+    t = int(t)
+    return t if 0 <= t < dvocab else int(dbos)
+
+
+def draft_model_rows(seq: Sequence[int], pos: int, ng: int, K: int, T_max: int, max_new: int, dvalid: int,
+                     dvocab: int, dbos: int, done: bool = False, slot: int = 0):
+    """First draft forward of one sequence: ``(d, catch_up, own)``, the rows as ``(tok, pos, slot, n_gen, max_new,
+    done)``.  The catch-up row is marked done: its K / V are written, the sampler skips it."""
+    d = 0 if done or slot < 0 else clip(K, pos, ng, K, T_max, max_new)
+    if d <= 0:
+        return 0, MASKED_ROW, MASKED_ROW
+    own = (draft_token(seq[pos], dvocab, dbos), pos, slot, ng, NO_BUDGET, 0)
+    if pos >= 1 and dvalid == pos - 1:
+        return d, (draft_token(seq[pos - 1], dvocab, dbos), pos - 1, slot, ng, NO_BUDGET, 1), own
+    return d, MASKED_ROW, own
+
+
+def draft_model_next(d_j: int, j: int, pos: int, ng: int, d: int, slot: int, dvocab: int, dbos: int):
+    """The row of draft forward ``j + 1`` from ``d_j``, the token forward ``j`` drew (``1 <= j <= d``)."""
+    if j + 1 > d:
+        return MASKED_ROW
+    return (draft_token(d_j, dvocab, dbos), pos + j, slot, ng + j, NO_BUDGET, 0)
+
+
+def draft_model_given(given, ng: int, drafts: Sequence[int], K: int) -> None:
+    """``d_1 .. d_d`` into the sequence's given buffer, ended when ``d < K``."""
+    d = len(drafts)
+    for j in range(1, d + 1):
+        given[ng + j - 1] = int(drafts[j - 1])
+    if d < K and ng + d < len(given):
+        given[ng + d] = -1
+
+
+def dvalid_after(pos: int, d: int, pos_after: int) -> int:
+    """``dvalid`` of a sequence that ran ``d >= 1`` draft forwards from ``pos`` and stands at ``pos_after``."""
+    return min(pos + d, pos_after)

@@ -170,6 +170,8 @@ class StudySettings:
     kv: str = "bf16"
     # on-device speculative decoding: n-gram drafts per decode step (0: off; the server's --speculative)
     speculative: int = 0
+    # ... drafted by this model instead ("": the n-gram lookup; the server's --draft-model TAG[=PATH])
+    draft_model: str = ""
     # weight storage of a "local:<device>" remote server ("" = the on-device arm's ``weights``: the reference's
     # Ollama served the same 4-bit builds in both arms)
     remote_weights: str = ""
@@ -411,6 +413,8 @@ class _StudyBase:
                 args += ["--kv", s.kv]
             if s.speculative and backend != "fake":
                 args += ["--speculative", str(s.speculative)]
+                if s.draft_model:
+                    args += ["--draft-model", s.draft_model]
             if s.trace:
                 args += ["--trace-dir", str(self.results_output_path / s.name / "traces" / f"rank{self.rank}")]
             env = {}

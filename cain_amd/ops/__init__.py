@@ -29,6 +29,9 @@ op                     source                      replaces (Ollama/llama.cpp)
 ``json_advance``       csrc/grammar.hip            the rows' automaton states over the sampled tokens
 ``spec_draft``         csrc/spec.hip               n-gram / given drafts -> K + 1 expanded rows per sequence
 ``spec_accept``        csrc/spec.hip               commit the longest correct draft prefix (lookup decoding)
+``spec_model_rows``    csrc/spec.hip               draft-model mode: the draft model's rows per forward, its tokens
+``spec_model_next``                                into the given drafts, ``dvalid`` per cache slot
+``spec_dvalid``
 ``Plan``               csrc/runtime.hip            per-step schedule + hipGraph replay
 =====================  ==========================  =============================
 """
@@ -1074,6 +1077,148 @@ def _np(t):
     import numpy as np
 
     return np.array(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+
+
+# ---- draft-model mode (csrc/spec.h CainSpecDraft)
+_SPECD_INTS = ("K", "dvocab", "dbos", "slots", "lds", "ldv", "ldg", "pad_")
+_SPECD_PTRS = ("seq", "given", "dvalid", "p0", "nd", "r_tok", "r_pos", "r_slot", "r_n_gen", "r_max_new", "r_done",
+               "r_hist", "r_gen", "r_params")
+_SPECD_ROWS = ("r_tok", "r_pos", "r_slot", "r_n_gen", "r_max_new", "r_done")
+
+
+class CainSpecDraft(ctypes.Structure):  # csrc/spec.h CainSpecDraft
+    _fields_ = [(n, ci) for n in _SPECD_INTS] + [(n, vp) for n in _SPECD_PTRS]
+
+
+def spec_draft_alloc(spec: dict, dvocab: int, dbos: int) -> dict:
+    """Buffers of draft-model mode beside the ``spec_alloc`` buffers ``spec`` (whose record and given drafts they
+    share): ``dvalid`` per cache slot, the step's scratch per sequence and the 2 R draft rows."""
+    R, T_max, dev = spec["nd"].shape[0], spec["seq"].shape[1], spec["seq"].device
+    if not 0 <= int(dbos) < int(dvocab):
+        raise ValueError(f"draft bos id {dbos} outside the draft vocabulary ({dvocab})")
+    z = lambda *s, dt=torch.int32: torch.zeros(*s, device=dev, dtype=dt)  # noqa: E731
+    return dict(K=int(spec["K"]), dvocab=int(dvocab), dbos=int(dbos), seq=spec["seq"], given=spec["given"],
+                dvalid=z(spec["seq"].shape[0]), p0=z(R), nd=z(R), r_tok=z(2 * R), r_pos=z(2 * R),
+                r_slot=torch.full((2 * R,), -1, device=dev, dtype=torch.int32), r_n_gen=z(2 * R), r_max_new=z(2 * R),
+                r_done=z(2 * R), r_hist=z(2 * R, 64), r_gen=z(2 * R, T_max),
+                r_params=z(2 * R * SAMPLE_BYTES, dt=torch.uint8))
+
+
+def spec_draft_struct(sd: dict) -> CainSpecDraft:
+    s = CainSpecDraft()
+    s.K, s.dvocab, s.dbos = int(sd["K"]), int(sd["dvocab"]), int(sd["dbos"])
+    s.slots, s.lds, s.ldv, s.ldg = sd["seq"].shape[0], sd["seq"].stride(0), sd["given"].stride(0), sd["r_gen"].stride(0)
+    for k in _SPECD_PTRS:
+        setattr(s, k, sd[k].data_ptr())
+    return s
+
+
+def load_spec_model() -> ctypes.CDLL:
+    """``load_spec()`` with the draft-model entry points' signatures set."""
+    lib = load_spec()
+    if not getattr(lib, "_cain_spec_model_sig", False):
+        lib.cain_spec_model_rows.argtypes = [vp, ci, ci] + [vp] * 9
+        lib.cain_spec_model_next.argtypes = [vp, ci, ci, ci, vp, vp, vp]
+        lib.cain_spec_dvalid.argtypes = [vp, ci, ci, vp, vp, vp]
+        lib.cain_plan_forward_spec_model.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
+        lib.cain_plan_capture_spec_model.restype = vp
+        lib.cain_plan_capture_spec_model.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, vp, ctypes.POINTER(ci)]
+        if int(lib.cain_spec_draft_size()) != ctypes.sizeof(CainSpecDraft):
+            raise NativeOpsUnavailable(f"{LIB_PATH}: CainSpecDraft is {int(lib.cain_spec_draft_size())} bytes, this "
+                                       f"package packs {ctypes.sizeof(CainSpecDraft)}: rebuild (python -m cain_amd.build)")
+        lib._cain_spec_model_sig = True
+    return lib
+
+
+def spec_model_rows(rows: dict, params: torch.Tensor, sd: dict, R: int, T_max: int) -> None:
+    """The 2 R rows of the first draft forward from sequences ``[0, R)`` of the decode rows."""
+    lib = load_spec_model()
+    _gpu(params, *[rows[k] for k in ROW_KEYS])
+    assert sd["nd"].shape[0] >= R and rows["tok"].shape[0] >= R
+    s = spec_draft_struct(sd)
+    _check(lib.cain_spec_model_rows(ctypes.byref(s), R, T_max, *[_p(rows[k]) for k in ROW_KEYS], _p(params),
+                                    _stream()), "spec_model_rows")
+
+
+def spec_model_next(rows: dict, sd: dict, R: int, j: int, T_max: int) -> None:
+    """After draft forward ``j``'s sampler: ``d_j`` into ``given``, the rows of forward ``j + 1``."""
+    lib = load_spec_model()
+    s = spec_draft_struct(sd)
+    _check(lib.cain_spec_model_next(ctypes.byref(s), R, j, T_max, _p(rows["slot"]), _p(rows["n_gen"]), _stream()),
+           "spec_model_next")
+
+
+def spec_dvalid(rows: dict, sd: dict, R: int, T_max: int) -> None:
+    """After accept: ``dvalid`` of the sequences' slots from their new positions."""
+    lib = load_spec_model()
+    s = spec_draft_struct(sd)
+    _check(lib.cain_spec_dvalid(ctypes.byref(s), R, T_max, _p(rows["slot"]), _p(rows["pos"]), _stream()),
+           "spec_dvalid")
+
+
+def spec_model_rows_ref(rows: dict, params, sd: dict, R: int, T_max: int) -> dict:
+    """``spec_model_rows`` from the rule (engine/speculative.py), sequence by sequence in Python: numpy arrays of
+    everything the kernel writes (the 2 R draft rows, ``p0``, ``nd``, ``given``)."""
+    import numpy as np
+
+    from ..engine import speculative as sp
+
+    K = int(sd["K"])
+    r = {k: _np(rows[k]) for k in ROW_KEYS}
+    hist = r["hist"].reshape(-1, 64)
+    par = _np(params).reshape(-1, SAMPLE_BYTES)
+    seq, dvalid = _np(sd["seq"]), _np(sd["dvalid"])
+    out = {k: np.zeros(2 * R, np.int32) for k in _SPECD_ROWS}
+    out.update(r_hist=np.zeros((2 * R, 64), np.int32), r_params=np.zeros((2 * R, SAMPLE_BYTES), np.uint8),
+               p0=np.zeros(R, np.int32), nd=np.zeros(R, np.int32), given=_np(sd["given"]))
+    for i in range(R):
+        sl, pos, ng, mn = int(r["slot"][i]), int(r["pos"][i]), int(r["n_gen"][i]), int(r["max_new"][i])
+        live = 0 <= sl < seq.shape[0] and not r["done"][i]
+        rec = list(seq[sl, :pos]) + [int(r["tok"][i])] if live else []
+        d, catch_up, own = sp.draft_model_rows(rec, pos, ng, K, T_max, mn, int(dvalid[sl]) if live else 0,
+                                               int(sd["dvocab"]), int(sd["dbos"]), done=not live, slot=sl)
+        out["p0"][i], out["nd"][i] = pos, d
+        if live and d < K:
+            out["given"][i, ng + d] = -1
+        for x, row in ((i, own), (R + i, catch_up)):
+            for k, v in zip(_SPECD_ROWS, row):
+                out[k][x] = v
+            out["r_hist"][x] = hist[i]
+            out["r_params"][x] = par[i]
+            out["r_params"][x, 20:36] = 0xFF  # eos_id and the three stop ids: -1
+    return out
+
+
+def spec_model_next_ref(rows: dict, sd: dict, R: int, j: int) -> dict:
+    """``spec_model_next`` from the rule: numpy copies of rows ``[0, R)`` (with their rings) and ``given`` after it."""
+    from ..engine import speculative as sp
+
+    out = {k: _np(sd[k])[:R] for k in _SPECD_ROWS}
+    out.update(r_hist=_np(sd["r_hist"])[:R], given=_np(sd["given"]))
+    slot, n_gen, p0, nd = _np(rows["slot"]), _np(rows["n_gen"]), _np(sd["p0"]), _np(sd["nd"])
+    for i in range(R):
+        d, ng = int(nd[i]), int(n_gen[i])
+        if d <= 0 or j > d:
+            continue
+        dj = int(out["r_tok"][i])
+        out["given"][i, ng + j - 1] = dj
+        out["r_hist"][i, (ng + j - 1) & 63] = dj
+        row = sp.draft_model_next(dj, j, int(p0[i]), ng, d, int(slot[i]), int(sd["dvocab"]), int(sd["dbos"]))
+        for k, v in zip(_SPECD_ROWS, row):
+            out[k][i] = v
+    return out
+
+
+def spec_dvalid_ref(rows: dict, sd: dict, R: int):
+    """``spec_dvalid`` from the rule: ``dvalid`` after it."""
+    from ..engine import speculative as sp
+
+    out = _np(sd["dvalid"])
+    slot, pos, p0, nd = _np(rows["slot"]), _np(rows["pos"]), _np(sd["p0"]), _np(sd["nd"])
+    for i in range(R):
+        if nd[i] > 0 and 0 <= slot[i] < out.shape[0]:
+            out[slot[i]] = sp.dvalid_after(int(p0[i]), int(nd[i]), int(pos[i]))
+    return out
 
 
 def spec_draft_ref(rows: dict, params, spec: dict, R: int, mode: int, T_max: int) -> dict:

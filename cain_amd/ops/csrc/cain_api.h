@@ -118,3 +118,10 @@ CAIN_API int cain_spec_draft(const CainSpec* s, int R, int T_max, const int* tok
 CAIN_API int cain_spec_accept(const CainSpec* s, int R, int T_max, int* tok, int* pos, const int* slot, int* n_gen,
                               const int* max_new, int* done, int* hist, int* gen, int ldg, const void* params,
                               hipStream_t st);
+CAIN_API int cain_spec_model_rows(const CainSpecDraft* s, int R, int T_max, const int* tok, const int* pos,
+                                  const int* slot, const int* n_gen, const int* max_new, const int* done,
+                                  const int* hist, const void* params, hipStream_t st);
+CAIN_API int cain_spec_model_next(const CainSpecDraft* s, int R, int j, int T_max, const int* slot, const int* n_gen,
+                                  hipStream_t st);
+CAIN_API int cain_spec_dvalid(const CainSpecDraft* s, int R, int T_max, const int* slot, const int* pos,
+                              hipStream_t st);

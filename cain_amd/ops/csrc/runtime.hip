@@ -333,6 +333,72 @@ bool spec_rows_ok(const Plan& p, int R, const CainRows* r, const CainSpec* s) {
   return R * (s->K + 1) <= max_rows(p.d) && s->vocab <= p.d.V;
 }
 
+// One speculative step whose drafts a draft model proposes (spec.h CainSpecDraft): the draft rows from the decode
+// state, the draft plan's forward over 2 R rows (each sequence's catch-up row and its own row, sampled with the
+// request's options), K - 1 further draft forwards over R rows, each fed by the token the one before sampled; every
+// sampled token lands in `given`, which the given-mode step then verifies.  `d2` / `d1`: the draft model's plans for
+// forwards of 2 R and of R rows (they differ in their attention split count only).  All on the one stream.
+int forward_spec_model(const Plan& p, const Plan& d2, const Plan& d1, int R, const CainRows& r, const CainSpec& s,
+                       const CainSpecDraft& sd, hipStream_t st) {
+  const int T = p.d.T_max;
+  CK(cain_spec_model_rows(&sd, R, T, r.tok, r.pos, r.slot, r.n_gen, r.max_new, r.done, r.hist, r.sample_params, st));
+  CainRows x{};
+  x.tok = sd.r_tok, x.pos = sd.r_pos, x.slot = sd.r_slot, x.n_gen = sd.r_n_gen, x.max_new = sd.r_max_new;
+  x.done = sd.r_done, x.hist = sd.r_hist, x.gen = sd.r_gen, x.ldg = sd.ldg, x.sample_params = sd.r_params;
+  CK(forward(d2, 2 * R, x, 1, 1, st));
+  for (int j = 1; j < sd.K; ++j) {
+    CK(cain_spec_model_next(&sd, R, j, T, r.slot, r.n_gen, st));
+    CK(forward(d1, R, x, 1, 1, st));
+  }
+  CK(cain_spec_model_next(&sd, R, sd.K, T, r.slot, r.n_gen, st));  // d_K into `given`
+  CK(forward_spec(p, R, r, s, st));
+  CK(cain_spec_dvalid(&sd, R, T, r.slot, r.pos, st));
+  return 0;
+}
+
+// What the _spec_model entries refuse before anything is launched: what spec_rows_ok refuses, a CainSpec that is not
+// in given mode over the draft record's own buffers, 2 R rows above what a forward of the draft plan may have, plans
+// of different T_max, a draft vocabulary beyond the draft plan's, a null buffer.
+bool spec_model_ok(const Plan& p, const Plan* d2, const Plan* d1, int R, const CainRows* r, const CainSpec* s,
+                   const CainSpecDraft* sd) {
+  if (!spec_rows_ok(p, R, r, s) || !d2 || !d1 || !sd) return false;
+  if (s->mode != 1 || sd->K != s->K || sd->given != s->given || sd->seq != s->seq || sd->ldv != s->ldv ||
+      sd->lds != s->lds || sd->slots != s->slots)
+    return false;
+  if (d2->d.T_max != p.d.T_max || d1->d.T_max != p.d.T_max || d2->d.V != d1->d.V) return false;
+  if (2 * R > max_rows(d2->d) || R > max_rows(d1->d)) return false;
+  if (sd->dvocab < 1 || sd->dvocab > d2->d.V || sd->dbos < 0 || sd->dbos >= sd->dvocab || sd->ldg < 1) return false;
+  return sd->dvalid && sd->p0 && sd->nd && sd->r_tok && sd->r_pos && sd->r_slot && sd->r_n_gen && sd->r_max_new &&
+         sd->r_done && sd->r_hist && sd->r_gen && sd->r_params && r->tok && r->pos && r->slot;
+}
+
+// `steps` calls of `step` recorded on `st` into one executable graph (null and *err on failure).
+template <class F>
+void* capture_steps(hipStream_t st, int steps, int* err, F step) {
+  hipGraph_t g = nullptr;
+  hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
+  if (e != hipSuccess) {
+    *err = int(e);
+    return nullptr;
+  }
+  int fe = 0;
+  for (int s = 0; s < steps && fe == 0; ++s) fe = step();
+  e = hipStreamEndCapture(st, &g);
+  if (fe != 0 || e != hipSuccess) {
+    *err = fe ? fe : int(e);
+    if (g) (void)hipGraphDestroy(g);
+    return nullptr;
+  }
+  hipGraphExec_t ex = nullptr;
+  e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(g);
+  if (e != hipSuccess) {
+    *err = int(e);
+    return nullptr;
+  }
+  return ex;
+}
+
 }  // namespace
 
 extern "C" {
@@ -454,28 +520,33 @@ CAIN_API void* cain_plan_capture_spec(void* plan, int R, const CainRows* rows, c
     *err = -1;
     return nullptr;
   }
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-  if (e != hipSuccess) {
-    *err = int(e);
+  return capture_steps(st, steps, err, [&] { return forward_spec(*p, R, *rows, *spec, st); });
+}
+
+// Speculative decoding with a draft model: one step (the draft plan's K forwards -> given-mode verify -> accept ->
+// dvalid) over the R sequences of `rows`; -1, with nothing launched, for what spec_model_ok refuses.
+CAIN_API int cain_plan_forward_spec_model(void* plan, void* draft2, void* draft1, int R, const CainRows* rows,
+                                          const CainSpec* spec, const CainSpecDraft* sd, hipStream_t st) {
+  auto* p = static_cast<Plan*>(plan);
+  auto *d2 = static_cast<Plan*>(draft2), *d1 = static_cast<Plan*>(draft1);
+  g_fail[0] = 0;
+  if (!p || !spec_model_ok(*p, d2, d1, R, rows, spec, sd)) return -1;
+  return forward_spec_model(*p, *d2, *d1, R, *rows, *spec, *sd, st);
+}
+
+// `steps` such steps in one graph (one stream: no parallel branch).
+CAIN_API void* cain_plan_capture_spec_model(void* plan, void* draft2, void* draft1, int R, const CainRows* rows,
+                                            const CainSpec* spec, const CainSpecDraft* sd, int steps, hipStream_t st,
+                                            int* err) {
+  auto* p = static_cast<Plan*>(plan);
+  auto *d2 = static_cast<Plan*>(draft2), *d1 = static_cast<Plan*>(draft1);
+  *err = 0;
+  if (!p || !spec_model_ok(*p, d2, d1, R, rows, spec, sd) || steps < 1) {
+    *err = -1;
     return nullptr;
   }
-  int fe = 0;
-  for (int s = 0; s < steps && fe == 0; ++s) fe = forward_spec(*p, R, *rows, *spec, st);
-  e = hipStreamEndCapture(st, &g);
-  if (fe != 0 || e != hipSuccess) {
-    *err = fe ? fe : int(e);
-    if (g) (void)hipGraphDestroy(g);
-    return nullptr;
-  }
-  hipGraphExec_t ex = nullptr;
-  e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (e != hipSuccess) {
-    *err = int(e);
-    return nullptr;
-  }
-  return ex;
+  return capture_steps(st, steps, err,
+                       [&] { return forward_spec_model(*p, *d2, *d1, R, *rows, *spec, *sd, st); });
 }
 
 CAIN_API int cain_graph_launch(void* exec, hipStream_t st) {

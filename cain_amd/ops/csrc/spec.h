@@ -38,4 +38,34 @@ struct CainSpec {
   int* step_tokens;  // [R][ldt]: tokens committed by step n_step % ldt
 };
 
+// Draft-model mode (engine/speculative.py "Draft model"): a second, smaller model with its own plan and KV cache
+// proposes the step's K tokens and writes them into CainSpec::given; verify and accept are given mode, unchanged.
+// The draft rows are the CainRows of the draft plan's forwards: row r < R is sequence r's sampled row (the input of
+// draft forward j at position pos + j - 1), row R + r its catch-up row at pos - 1 (first forward only).
+struct CainSpecDraft {
+  int K;       // 1 .. SPEC_K_MAX (the CainSpec's)
+  int dvocab;  // rows of the draft model's embedding: a token id outside [0, dvocab) enters as `dbos`
+  int dbos;    // the draft model's bos id, in [0, dvocab)
+  int slots;   // rows of `seq` and entries of `dvalid` (cache slots of both models)
+  int lds;     // row stride of `seq` (>= T_max)
+  int ldv;     // row stride of `given`
+  int ldg;     // row stride of r_gen
+  int pad_;
+  const int* seq;  // CainSpec::seq
+  int* given;      // CainSpec::given: the drafts of generated index n at [r][n]
+  int* dvalid;     // [slots]: leading positions of the slot's draft cache that hold K / V of seq
+  int* p0;         // [R]: the sequence's position before the step
+  int* nd;         // [R]: draft forwards the sequence is live for this step (d; 0: none)
+  // the draft rows, 2 R of them
+  int* r_tok;
+  int* r_pos;
+  int* r_slot;
+  int* r_n_gen;
+  int* r_max_new;
+  int* r_done;
+  int* r_hist;     // [2 R][64]
+  int* r_gen;      // [2 R][ldg]: the sampler's output ring of the draft rows (scratch)
+  void* r_params;  // [2 R] SampleParams: the request's own, stop ids off
+};
+
 }  // extern "C"

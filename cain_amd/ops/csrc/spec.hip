@@ -10,6 +10,10 @@
 //                       written in, sampling options) are written for the verify forward.
 //   spec_accept_kernel  one wave per sequence: lane j holds the token the sampler drew for row j; a ballot finds the
 //                       first draft that differs, lane 0 commits t_0 .. t_a with the sampler's advance_row semantics.
+//   spec_model_rows_kernel / spec_model_next_kernel / spec_dvalid_kernel
+//                       draft-model mode: the rows of the draft model's forwards (first forward from the decode state,
+//                       forward j + 1 from the sampler's output of forward j, which also goes into `given`) and the
+//                       per-slot count of draft-cache positions that hold the sequence's own tokens.
 //
 // Integer work only, plain vector loads and stores, no atomics.
 #include "cain_api.h"
@@ -164,6 +168,92 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(CainSpec s, int T_max, 
   }
 }
 
+// ---- draft-model mode (spec.h CainSpecDraft; engine/speculative.py "Draft model") ----------------------------------
+constexpr int SPEC_NO_BUDGET = 0x7fffffff;
+
+__device__ __forceinline__ int draft_token(const CainSpecDraft& s, int t) {
+  return t >= 0 && t < s.dvocab ? t : s.dbos;  // the draft embedding is never indexed out of range
+}
+
+__device__ __forceinline__ void draft_row(const CainSpecDraft& s, int x, int tok, int pos, int slot, int n_gen,
+                                          int max_new, int done) {
+  s.r_tok[x] = tok, s.r_pos[x] = pos, s.r_slot[x] = slot, s.r_n_gen[x] = n_gen, s.r_max_new[x] = max_new;
+  s.r_done[x] = done;
+}
+
+// The rows of the first draft forward, one workgroup per sequence: row r is the sequence's own token at `pos`, sampled
+// with the request's options (stop ids off, no budget); row R + r the catch-up at pos - 1, run (KV only: it is
+// marked done, which the sampler skips) when the slot's draft cache ends one position short.  A sequence that drafts
+// nothing (done, masked, or on its last token) has both rows masked.
+__global__ __launch_bounds__(SPEC_THREADS) void spec_model_rows_kernel(CainSpecDraft s, int R, int T_max,
+                                                                      const int* __restrict__ tok,
+                                                                      const int* __restrict__ pos,
+                                                                      const int* __restrict__ slot,
+                                                                      const int* __restrict__ n_gen,
+                                                                      const int* __restrict__ max_new,
+                                                                      const int* __restrict__ done,
+                                                                      const int* __restrict__ hist,
+                                                                      const uint32_t* __restrict__ params) {
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int sl = slot[r], p = pos[r], ng = n_gen[r], mn = max_new[r], dn = done[r];
+  const bool live = sl >= 0 && sl < s.slots && !dn && p >= 0 && p < T_max && ng >= 0;
+  const int d = live ? max(0, min(s.K, min(T_max - 1 - p, mn - 1 - ng))) : 0;
+  if (tid == 0) {
+    s.p0[r] = p;
+    s.nd[r] = d;
+    if (live && d < s.K && ng + d < s.ldv) s.given[(size_t)r * s.ldv + ng + d] = -1;
+    const bool catch_up = d > 0 && p >= 1 && s.dvalid[sl] == p - 1;
+    if (d > 0) draft_row(s, r, draft_token(s, tok[r]), p, sl, ng, SPEC_NO_BUDGET, 0);
+    else draft_row(s, r, 0, 0, -1, 0, 0, 0);
+    if (catch_up) draft_row(s, R + r, draft_token(s, s.seq[(size_t)sl * s.lds + p - 1]), p - 1, sl, ng, SPEC_NO_BUDGET, 1);
+    else draft_row(s, R + r, 0, 0, -1, 0, 0, 0);
+  }
+  for (int e = tid; e < 2 * SPEC_HIST; e += SPEC_THREADS) {
+    const int x = e < SPEC_HIST ? r : R + r, h = e & (SPEC_HIST - 1);
+    s.r_hist[(size_t)x * SPEC_HIST + h] = hist[(size_t)r * SPEC_HIST + h];
+  }
+  uint32_t* xp = static_cast<uint32_t*>(s.r_params);
+  for (int e = tid; e < 2 * SPEC_PARAM_DW; e += SPEC_THREADS) {
+    const int x = e < SPEC_PARAM_DW ? r : R + r, w = e % SPEC_PARAM_DW;
+    xp[(size_t)x * SPEC_PARAM_DW + w] = w >= 5 && w <= 8 ? 0xffffffffu : params[(size_t)r * SPEC_PARAM_DW + w];
+  }
+}
+
+// After the sampler of draft forward j (1 .. K): d_j, the token it left in row r, goes into `given` at generated index
+// ng + j - 1 and into the row's ring, and row r becomes the input of forward j + 1 -- or is masked when j + 1 > d.
+__global__ __launch_bounds__(64) void spec_model_next_kernel(CainSpecDraft s, int R, int j,
+                                                             const int* __restrict__ slot,
+                                                             const int* __restrict__ n_gen) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= R) return;
+  const int d = s.nd[r];
+  if (d <= 0 || j > d) return;  // the row is masked already
+  const int ng = n_gen[r], dj = s.r_tok[r];
+  if (ng + j - 1 < s.ldv) s.given[(size_t)r * s.ldv + ng + j - 1] = dj;
+  s.r_hist[(size_t)r * SPEC_HIST + ((ng + j - 1) & (SPEC_HIST - 1))] = dj;
+  if (j + 1 <= d) draft_row(s, r, draft_token(s, dj), s.p0[r] + j, slot[r], ng + j, SPEC_NO_BUDGET, 0);
+  else draft_row(s, r, 0, 0, -1, 0, 0, 0);
+}
+
+// After accept: positions pos0 .. pos0 + d - 1 of the slot's draft cache hold the sequence's token and d_1 .. d_{d-1};
+// those below the sequence's new position are tokens of its record.
+__global__ __launch_bounds__(64) void spec_dvalid_kernel(CainSpecDraft s, int R, const int* __restrict__ slot,
+                                                         const int* __restrict__ pos) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= R) return;
+  const int d = s.nd[r], sl = slot[r];
+  if (d > 0 && sl >= 0 && sl < s.slots) s.dvalid[sl] = min(s.p0[r] + d, pos[r]);
+}
+
+int spec_model_ok(const CainSpecDraft* s, int R, int T_max) {
+  if (!s || R < 1 || s->K < 1 || s->K > SPEC_K_MAX || T_max < 1) return 0;
+  if (s->dvocab < 1 || s->dbos < 0 || s->dbos >= s->dvocab || s->slots < 1 || s->lds < T_max || s->ldv < 1 ||
+      s->ldg < 1)
+    return 0;
+  return s->seq && s->given && s->dvalid && s->p0 && s->nd && s->r_tok && s->r_pos && s->r_slot && s->r_n_gen &&
+         s->r_max_new && s->r_done && s->r_hist && s->r_gen && s->r_params;
+}
+
 int spec_ok(const CainSpec* s, int R, int T_max) {
   if (!s || R < 1 || s->K < 1 || s->K > SPEC_K_MAX || (s->mode != 0 && s->mode != 1)) return 0;
   if (s->slots < 1 || s->lds < T_max || T_max < 1 || s->ldt < 1 || s->ldg < 1 || s->vocab < 1) return 0;
@@ -197,3 +287,32 @@ CAIN_API int cain_spec_accept(const CainSpec* s, int R, int T_max, int* tok, int
 }
 
 CAIN_API int cain_spec_size() { return int(sizeof(CainSpec)); }
+
+// Draft-model mode.  Rows [0, R) of the decode state -> the 2 R rows of the first draft forward.
+CAIN_API int cain_spec_model_rows(const CainSpecDraft* s, int R, int T_max, const int* tok, const int* pos,
+                                  const int* slot, const int* n_gen, const int* max_new, const int* done,
+                                  const int* hist, const void* params, hipStream_t st) {
+  if (!spec_model_ok(s, R, T_max) || !tok || !pos || !slot || !n_gen || !max_new || !done || !hist || !params)
+    return -1;
+  hipLaunchKernelGGL(spec_model_rows_kernel, dim3(R), dim3(SPEC_THREADS), 0, st, *s, R, T_max, tok, pos, slot, n_gen,
+                     max_new, done, hist, static_cast<const uint32_t*>(params));
+  return int(hipGetLastError());
+}
+
+// After draft forward j's sampler: d_j into `given`, rows [0, R) become the input of forward j + 1.
+CAIN_API int cain_spec_model_next(const CainSpecDraft* s, int R, int j, int T_max, const int* slot, const int* n_gen,
+                                  hipStream_t st) {
+  if (!spec_model_ok(s, R, T_max) || j < 1 || j > s->K || !slot || !n_gen) return -1;
+  hipLaunchKernelGGL(spec_model_next_kernel, dim3((R + 63) / 64), dim3(64), 0, st, *s, R, j, slot, n_gen);
+  return int(hipGetLastError());
+}
+
+// After cain_spec_accept: the slots' dvalid from the sequences' new positions.
+CAIN_API int cain_spec_dvalid(const CainSpecDraft* s, int R, int T_max, const int* slot, const int* pos,
+                              hipStream_t st) {
+  if (!spec_model_ok(s, R, T_max) || !slot || !pos) return -1;
+  hipLaunchKernelGGL(spec_dvalid_kernel, dim3((R + 63) / 64), dim3(64), 0, st, *s, R, slot, pos);
+  return int(hipGetLastError());
+}
+
+CAIN_API int cain_spec_draft_size() { return int(sizeof(CainSpecDraft)); }

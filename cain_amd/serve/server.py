@@ -183,7 +183,8 @@ class EngineBackend(Backend):
     def __init__(self, models: List[str], device: str = "cuda:0", max_batch: int = 16, max_context: int = 2048,
                  backend: Optional[str] = None, seed: int = 0, preload: bool = False, steps_per_graph: int = 8,
                  trace_dir: Optional[str] = None, weight_dtype: str = "bf16", continuous: bool = True,
-                 kv_dtype: str = "bf16", prefix_cache: bool = False, speculative: int = 0):
+                 kv_dtype: str = "bf16", prefix_cache: bool = False, speculative: int = 0,
+                 draft_model: Optional[str] = None):
         self._models = list(models)
         self.prefix_cache = bool(prefix_cache)
         self.speculative = int(speculative)  # drafts per decode step (engine/speculative.py); 0: off
@@ -191,6 +192,9 @@ class EngineBackend(Backend):
             raise ValueError(f"speculative must be in 0..7, got {speculative}")
         if self.speculative and self.prefix_cache:
             raise ValueError("speculative decoding and prefix_cache cannot be combined")
+        self.draft_model = draft_model or None  # tag of the model that drafts (engine/speculative.py "Draft model")
+        if self.draft_model and not self.speculative:
+            raise ValueError("draft_model needs speculative > 0")
         self.kv_dtype = kv_dtype
         # continuous batching needs the HIP engine; tracing records whole static batches
         self.continuous = continuous and not trace_dir
@@ -215,6 +219,13 @@ class EngineBackend(Backend):
     def max_batch(self, model: str) -> int:
         return self._max_batch
 
+    @property
+    def speculative_label(self) -> str:
+        """What ``/api/show`` and ``/api/ps`` report as "speculative" ("": the mode is off)."""
+        if not self.speculative:
+            return ""
+        return f"draft:{self.draft_model}-k{self.speculative}" if self.draft_model else f"ngram-k{self.speculative}"
+
     def engine(self, model: str):
         from ..engine import DecodeEngine
 
@@ -227,7 +238,7 @@ class EngineBackend(Backend):
                                    max_context=self.max_context, backend=self.backend, seed=self.seed,
                                    steps_per_graph=self.steps_per_graph, weight_dtype=self.weight_dtype,
                                    kv_dtype=self.kv_dtype, prefix_cache=self.prefix_cache,
-                                   speculative=self.speculative)
+                                   speculative=self.speculative, draft_model=self.draft_model)
                 self.engines[model] = eng
             return eng
 
@@ -266,7 +277,7 @@ class EngineBackend(Backend):
                            "quantization_level": QUANT_LEVEL[self.weight_dtype], "format": "cain-packed"},
                "model_info": info}
         if self.speculative:
-            out["details"]["speculative"] = f"ngram-k{self.speculative}"
+            out["details"]["speculative"] = self.speculative_label
         if ckpt:  # as Ollama's show: the prompt template and the stop tokens (a checkpoint's)
             from ..models.hf import load_tokenizer
 
@@ -626,7 +637,8 @@ class OllamaHandler(BaseHTTPRequestHandler):
             be = self.scheduler.backend
             self._send_json(200, {"models": [{"name": m, "model": m, "expires_at": "2999-01-01T00:00:00Z",
                                               "prefix_cache": bool(getattr(be, "prefix_cache", False)),
-                                              **({"speculative": f"ngram-k{be.speculative}"}
+                                              **({"speculative": getattr(be, "speculative_label", "")
+                                                  or f"ngram-k{be.speculative}"}
                                                  if getattr(be, "speculative", 0) else {})}
                                              for m in self.scheduler.queues]})
         else:
@@ -832,6 +844,9 @@ def main(argv: Optional[List[str]] = None) -> None:
                     help="speculative decoding: K (1..7) n-gram drafts from the request's own tokens per decode step, "
                          "verified K + 1 rows per weight pass; the tokens are plain decoding's (not with "
                          "--prefix-cache or logprobs)")
+    ap.add_argument("--draft-model", default=None, metavar="TAG[=PATH]",
+                    help="with --speculative: a smaller model with the same tokenizer proposes the K drafts inside "
+                         "the decode graphs instead of the n-gram lookup (PATH: its checkpoint, as --checkpoint)")
     ap.add_argument("--checkpoint", action="append", metavar="TAG=PATH",
                     help="serve a Hugging Face checkpoint directory or GGUF file under TAG (repeatable; models/hf.py); "
                          "PATH 'ollama' takes the blob a local Ollama store keeps for TAG")
@@ -847,19 +862,31 @@ def main(argv: Optional[List[str]] = None) -> None:
         raise SystemExit("--speculative must be in 0..7")
     if ns.speculative and ns.prefix_cache:
         raise SystemExit("--speculative and --prefix-cache cannot be combined")
+    draft = _draft_model_arg(ns.draft_model, ns.speculative)
     if ns.backend == "fake":
         be: Backend = FakeBackend(models, tokens_per_s=ns.fake_tok_s, prefill_s=ns.fake_prefill_s)
     else:
         be = EngineBackend(models, device=ns.device, max_batch=ns.max_batch, max_context=ns.max_context,
                            backend=ns.backend, preload=ns.preload, trace_dir=ns.trace_dir, weight_dtype=ns.weights,
                            continuous=not ns.static_batching, kv_dtype=ns.kv, prefix_cache=ns.prefix_cache,
-                           speculative=ns.speculative)
+                           speculative=ns.speculative, draft_model=draft)
     srv = make_server(be, ns.host, ns.port, ns.batch_window_ms, ns.verbose)
     print(f"[serve] Ollama-compatible API on http://{ns.host}:{srv.server_address[1]} models={models}", flush=True)
     try:
         srv.serve_forever()
     except KeyboardInterrupt:  # pragma: no cover
         pass
+
+
+def _draft_model_arg(arg: Optional[str], speculative: int) -> Optional[str]:
+    """``--draft-model TAG[=PATH]``: the tag, its checkpoint registered when a path is given."""
+    if not arg:
+        return None
+    if not speculative:
+        raise SystemExit("--draft-model needs --speculative K")
+    if "=" in arg:
+        register_checkpoints([arg])
+    return arg.split("=", 1)[0]
 
 
 def generate_main(argv: Optional[List[str]] = None) -> None:
@@ -875,13 +902,15 @@ def generate_main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16")
     ap.add_argument("--checkpoint", metavar="PATH", help="a Hugging Face checkpoint directory, served as --model")
     ap.add_argument("--speculative", type=int, default=0, metavar="K", help="speculative decoding with K n-gram drafts")
+    ap.add_argument("--draft-model", default=None, metavar="TAG[=PATH]",
+                    help="with --speculative: the model that proposes the drafts")
     ap.add_argument("--format", choices=["json"], default=None,
                     help="json: constrain the output to a JSON object (Ollama's format: \"json\")")
     ns = ap.parse_args(argv)
     if ns.checkpoint:
         register_checkpoints([f"{ns.model}={ns.checkpoint}"])
     be = EngineBackend([ns.model], device=ns.device, max_batch=1, weight_dtype=ns.weights, kv_dtype=ns.kv,
-                       speculative=ns.speculative)
+                       speculative=ns.speculative, draft_model=_draft_model_arg(ns.draft_model, ns.speculative))
     opts = {k: v for k, v in (("temperature", ns.temperature), ("seed", ns.seed)) if v is not None}
     job = Job(ns.model, ns.prompt, ns.num_predict or default_num_predict(ns.prompt), opts, format=ns.format)
     if ns.format:

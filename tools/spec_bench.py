@@ -11,6 +11,8 @@ Per model and weight format, on one GPU:
    configuration; medians.  ``plain_prefix``: how many leading tokens equal the plain engine's (a K + 1-row forward
    rounds differently from a 1-row one; a deep random-init stack parts at the first near-tie).
 3. ``ngram``: the n-gram mode's acceptance on the model's own greedy decode (random-init weights: not natural text).
+4. ``draft`` (``--draft-model TAG``, instead of 1 - 3; profiles/r16/draft_model/README.md): ms per plain, n-gram and
+   draft-model step at K = ``--rate-k``, the break-even tokens per step and the measured ones.
 
 One JSON line per measurement on stdout (and in ``--out``).
 """
@@ -42,6 +44,45 @@ def common(a, b) -> int:
     return n
 
 
+def draft_model_bench(model, draft, wd, k, n, repeats, run, emit) -> None:
+    """``kind="draft"``: ms per plain step, per n-gram speculative step and per draft-model step (interleaved,
+    medians), the tokens a draft-model step has to commit to break even with plain decoding, and the tokens it did
+    commit on the model's own greedy decode (random-init weights: not natural text)."""
+    import torch
+
+    from cain_amd.engine import DecodeEngine
+    from cain_amd.models import get_config, random_weights
+
+    w = random_weights(get_config(model), device=torch.device("cuda"), seed=0)
+    kw = dict(device="cuda", max_batch=1, max_context=1024, weights=w, weight_dtype=wd, keep_natural=True,
+              steps_per_graph=8)
+    engines = dict(plain=DecodeEngine(model, **kw), ngram=DecodeEngine(model, speculative=k, **kw),
+                   draft=DecodeEngine(model, speculative=k, draft_model=w if draft == "self" else draft, **kw))
+    for e in engines.values():  # warm: graphs captured
+        run(e, n)
+    ms = {name: [] for name in engines}
+    last = {}
+    for _ in range(repeats):
+        for name, e in engines.items():
+            r, t, _ = run(e, n)
+            ms[name].append(t * 1e3 / (r.decode_steps or n))
+            last[name] = r
+    med = {name: statistics.median(v) for name, v in ms.items()}
+    r = last["draft"]
+    emit(kind="draft", model=model, draft=draft, weights=wd, K=k, plain_ms_per_step=round(med["plain"], 4),
+         ngram_ms_per_step=round(med["ngram"], 4), draft_ms_per_step=round(med["draft"], 4),
+         break_even_tokens_per_step=round(med["draft"] / med["plain"], 3),
+         tokens_per_step=round(r.eval_count / max(1, r.decode_steps), 3),
+         ngram_tokens_per_step=round(last["ngram"].eval_count / max(1, last["ngram"].decode_steps), 3),
+         drafted=r.draft_count, accepted=r.draft_accepted,
+         same_tokens_as_ngram_engine=r.tokens == last["ngram"].tokens,
+         note="random-init weights: acceptance is not representative of natural text")
+    for e in engines.values():
+        e.close()
+    del engines, w
+    torch.cuda.empty_cache()
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="llama3.1:8b,qwen2:1.5b")
@@ -50,6 +91,9 @@ def main(argv=None) -> int:
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--ks", default="1,3,7")
     ap.add_argument("--rate-k", type=int, default=3, help="K of the acceptance-rate sweep")
+    ap.add_argument("--draft-model", default=None, metavar="TAG",
+                    help="measure draft-model mode instead (K = --rate-k): TAG drafts for each of --models; 'self': "
+                         "the target's own weights, which accepts everything up to rounding (the upper bound)")
     ap.add_argument("--no-energy", action="store_true")
     ap.add_argument("--out", default=None)
     ns = ap.parse_args(argv)
@@ -85,6 +129,11 @@ def main(argv=None) -> int:
         return r, eng.last_decode_ns * 1e-9, (rd.gpu_energy_j if rd is not None else None)
 
     n, ks = ns.tokens, [int(k) for k in ns.ks.split(",")]
+    if ns.draft_model:
+        for model in ns.models.split(","):
+            for wd in ns.weights.split(","):
+                draft_model_bench(model, ns.draft_model, wd, ns.rate_k, n, ns.repeats, run, emit)
+        return 0
     for model in ns.models.split(","):
         for wd in ns.weights.split(","):
             cfg = get_config(model)
