@@ -535,17 +535,20 @@ def w4_variant(n: int, k: int, m: int, epi: int = EPI_BF16) -> int:
     return int(load().cain_gemm_w4_variant(int(n), int(k), int(m), int(epi)))
 
 
-def quant_rows(x: torch.Tensor, norm: bool = False, eps: float = 1e-6):
+def quant_rows(x: torch.Tensor, norm: bool = False, eps: float = 1e-6, x8: Optional[torch.Tensor] = None):
     """Per-row e4m3 quantisation of bf16 activations (csrc/wgemm8.hip quant_rows_kernel): returns (x8 uint8
-    [M, K], xs fp32 [M]) with x ~= e4m3(x8) * amax/448 and xs = amax/448 * (rsqrt(mean(x^2) + eps) if norm)."""
+    [M, K], xs fp32 [M]) with x ~= e4m3(x8) * amax/448 and xs = amax/448 * (rsqrt(mean(x^2) + eps) if norm).
+    ``x8``: the output rows, uint8 [M, K] of any row pitch (a view into a wider buffer, as the runtime's)."""
     lib = load()
-    _gpu(x)
+    _gpu(x, x8)
     M, K = x.shape
     assert x.dtype == torch.bfloat16 and x.stride(1) == 1
-    x8 = torch.empty(M, K, device=x.device, dtype=torch.uint8)
+    if x8 is None:
+        x8 = torch.empty(M, K, device=x.device, dtype=torch.uint8)
+    assert x8.dtype == torch.uint8 and x8.shape == (M, K) and x8.stride(1) == 1, (x8.dtype, tuple(x8.shape))
     xs = torch.empty(M, device=x.device, dtype=torch.float32)
-    _check(lib.cain_quant_rows(_p(x), x.stride(0), K, M, _p(x8), K, _p(xs), int(bool(norm)), eps, _stream()),
-           "quant_rows")
+    _check(lib.cain_quant_rows(_p(x), x.stride(0), K, M, _p(x8), x8.stride(0), _p(xs), int(bool(norm)), eps,
+                               _stream()), "quant_rows")
     return x8, xs
 
 

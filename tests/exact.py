@@ -27,6 +27,25 @@ the rotation is a signed permutation of those bf16 values, exact.  An fp8 KV cac
 
 Where exactness is impossible (fused RMSNorm, SiLU / GeLU) ``tile_err`` replaces the whole-matrix norm, against
 limits of ``FLOOR_FACTOR`` x the measured floors in ``TILE_FLOORS``.
+
+Fused QKV geometries.  ``QKV_CASES`` run at (H, Hkv, hd, T_max) = 2 / 1 / 32 / 64, where much of the epilogue's index
+arithmetic collapses; ``QKV_GEO_CASES`` repeat every family at the models' head shapes (``QKV_GEOS``), with idle rows
+(slot -1) and rows that share a slot (``qkv_rows``).  ``epi_mirror`` walks the epilogue's addressing on the host with
+one fault planted at a time, and ``qkv_mismatch`` must report it wherever it can show (``QKV_FAULT_SHOWS``, checked by
+tests/test_exact_cpu.py):
+
+    fault                                   toy 2/1/32   phi3 4/4/96   gqa 4/2/128   gemma 2/1/256
+    hkv   Hkv dropped from the cache base   invisible    caught        caught        invisible (Hkv = 1)
+    tph   tiles per head -> power of two    invisible    caught        invisible     invisible (2, 6, 8, 16 tiles)
+    idle  an idle row written               no idle row  caught        caught        caught
+    d5    d >> 5 dropped from kfrag_off     invisible    caught        caught        caught (hd >> 5 = 1, 3, 4, 8)
+    b2    partner bias from b1's rows       caught       caught        caught        caught
+
+Row ops (tests/test_rowops_exact_gpu.py, host twin tests/test_rowops_exact_cpu.py): ``quant_rows_ref`` states
+quant_rows byte for byte -- on rows whose amax is 448 2^e the scale and its inverse are powers of two and the e4m3
+bytes are exact (``quant_exact_rows``); on random rows every element is held to half an e4m3 step
+(``quant_general_mismatch``); the folded RMSNorm factor is checked on sparse integer rows whose sum of squares is
+exact (``quant_norm_rows``).  ``embed_ref`` is bit-exact, ``rmsnorm_mismatch`` allows one bf16 step.
 """
 from __future__ import annotations
 
@@ -222,10 +241,12 @@ class Case:
     amp: int = 2       # activations (and bf16 weights) in -amp..amp
     density: float = 1.0
     small: bool = False  # small block scales (fp8 KV: |values| <= 448)
+    geo: str = ""      # fused QKV: a key of QKV_GEOS ("": the 2 / 1 / 32 / 64 geometry of QKV_CASES)
 
     @property
     def id(self) -> str:
-        return f"{self.fam}-{self.tag + '-' if self.tag else ''}N{self.N}-K{self.K}-M{self.M}"
+        tag = "-".join(t for t in (self.tag, self.geo) if t)
+        return f"{self.fam}-{tag + '-' if tag else ''}N{self.N}-K{self.K}-M{self.M}"
 
 
 def a8_plant(c: Case) -> int:
@@ -290,15 +311,36 @@ CASES = _cases()
 #: fused QKV + RoPE + KV-append geometry of the exact cases: 2 q heads, 1 kv head of 32 dims = 8 tiles
 QKV_H, QKV_HKV, QKV_HD, QKV_TMAX = 2, 1, 32, 64
 QKV_N = (QKV_H + 2 * QKV_HKV) * QKV_HD
+Geo = Tuple[int, int, int, int]  # (H, Hkv, hd, T_max)
+QKV_GEO: Geo = (QKV_H, QKV_HKV, QKV_HD, QKV_TMAX)
+
+#: the models' head geometries (module doc, "Fused QKV geometries"); T_max = 96 is no power of two: 6 K blocks of 16
+#: positions, 3 V^T blocks of 32
+QKV_GEOS: Dict[str, Geo] = {
+    "phi3": (4, 4, 96, 96),    # MHA; 6 tiles per head (no power of two)
+    "gqa": (4, 2, 128, 96),    # Hkv > 1; hd >> 5 = 4 fragments per K block
+    "gemma": (2, 1, 256, 96),  # hd >> 4 = 16 V tiles per block
+}
 
 
-def qkv_case(fam: str, K: int, M: int, kv8: bool) -> Case:
+def case_geo(c: "Case") -> Geo:
+    return QKV_GEOS[c.geo] if c.geo else QKV_GEO
+
+
+def qkv_n(geo: Geo) -> int:
+    H, Hkv, hd, _ = geo
+    return (H + 2 * Hkv) * hd
+
+
+def qkv_case(fam: str, K: int, M: int, kv8: bool, geo: str = "") -> Case:
     """fp8 KV: sparse activations and small block scales keep |k|, |v| <= 448 (no e4m3 saturation); on the
-    activation-quantised families the planted row maximum is 7 / 14 instead of 448 (``int_x``)."""
+    activation-quantised families the planted row maximum is 7 / 14 instead of 448 (``int_x``).  ``geo``: a key of
+    ``QKV_GEOS`` ("": ``QKV_GEO``)."""
+    N = qkv_n(QKV_GEOS[geo] if geo else QKV_GEO)
     if kv8:
-        return Case(fam, QKV_N, K, M, "qkv8", amp=3 if fam in ("w8a8", "w4a8") else 1, density=8.0 / K,
-                    small=fam in ("q4_k", "q6", "w8a8"))
-    return Case(fam, QKV_N, K, M, "qkv", amp=2 if fam != "bf16" or M <= 64 else 1)
+        return Case(fam, N, K, M, "qkv8", amp=3 if fam in ("w8a8", "w4a8") else 1, density=8.0 / K,
+                    small=fam in ("q4_k", "q6", "w8a8"), geo=geo)
+    return Case(fam, N, K, M, "qkv", amp=2 if fam != "bf16" or M <= 64 else 1, geo=geo)
 
 
 #: (family, K, row counts) of the QKV cases; the Q4 / Q6 row counts straddle their launches (4 rows at K = 3072)
@@ -307,6 +349,42 @@ QKV_SHAPES = [("bf16", 1056, (1, 16)), ("bf16", 512, (40,)), ("bf16", 1024, (129
               ("w8a8", 640, (40,)), ("w4a8", 640, (40,))]
 QKV_ROWS = {3072: 4}
 QKV_CASES = [qkv_case(f, k, m, kv8) for f, k, ms in QKV_SHAPES for m in ms for kv8 in (False, True)]
+
+#: one row count per (family, K) of QKV_SHAPES at each geometry of QKV_GEOS, across a row-block or launch boundary
+#: where the path has one: the skinny kernel's single 16-row block full; 2.5 row blocks of 16 (batched bf16, fp8 and
+#: MXFP4 weights); 129 rows = the wide kernels' 128-row tile + 1 (bf16 and the activation-quantised pair, which then
+#: run their 256-row tile); Q4 / Q6: 2 launches of QKV_ROWS rows + 1.  No family is dropped from any geometry.
+QKV_GEO_ROWS = {("bf16", 1056): 16, ("bf16", 512): 40, ("bf16", 1024): 129, ("w8", 1088): 40, ("w4", 1920): 40,
+                ("q4_0", 3072): 9, ("q4_k", 3072): 9, ("q6", 3072): 9, ("w8a8", 640): 129, ("w4a8", 640): 129}
+QKV_GEO_CASES = [qkv_case(f, k, QKV_GEO_ROWS[f, k], kv8, geo) for geo in QKV_GEOS for f, k, _ in QKV_SHAPES
+                 for kv8 in (False, True)]
+
+
+def qkv_rows(M: int, T_max: int, seed: int):
+    """(slot int32 [M], pos int32 [M], S) of one fused-QKV launch over S cache slots.
+
+    What a prefill chunk or the K + 1 verify rows of speculative decoding look like, plus masked rows --
+    * about a quarter of the rows, always the first and the last, are idle: slot -1 (pos 0: a masked row's position
+      is unspecified, the kernel may read its tables);
+    * five live rows share one slot at positions 15, 16 (two K blocks), 31, 32 (two V^T blocks) and T_max - 1;
+    * the other live rows draw distinct (slot, position) pairs, so every cache element has at most one owner;
+    * the live rows stand in random order, so the shared slot's rows fall into different row blocks / launches."""
+    g = _gen(seed)
+    assert M >= 8 and T_max > 33
+    S = max(3, (M + 3) // 4)
+    inner = 1 + torch.randperm(M - 2, generator=g)
+    idle = torch.cat([torch.tensor([0, M - 1]), inner[: max(2, M // 4) - 2]])
+    live = inner[max(2, M // 4) - 2:]  # already in random order
+    slot = torch.full((M,), -1, dtype=torch.int32)
+    pos = torch.zeros(M, dtype=torch.int32)
+    s0 = int(torch.randint(0, S, (1,), generator=g))
+    fixed = [15, 16, 31, 32, T_max - 1]
+    free = [i for i in torch.randperm(S * T_max, generator=g).tolist() if not (i // T_max == s0 and i % T_max in fixed)]
+    pairs = [(s0, p) for p in fixed] + [(i // T_max, i % T_max) for i in free[: len(live) - len(fixed)]]
+    for m, (s, p) in zip(live.tolist(), pairs):
+        slot[m], pos[m] = s, p
+    assert len(idle) + len(pairs) == M
+    return slot, pos, S
 
 
 def plain_extras(c: Case):
@@ -583,6 +661,429 @@ def qkv_expected(proj: torch.Tensor, pos: torch.Tensor, cos: torch.Tensor, sin: 
     k = rot(nat[:, H * hd:(H + Hkv) * hd].view(M, Hkv, hd), c, s)
     v = nat[:, (H + Hkv) * hd:].view(M, Hkv, hd)
     return q, k, v
+
+
+def qkv_launch(c: Case):
+    """(bias [N] int64 in the kernel's row order, slot, pos, S, cos, sin) of a fused-QKV case: the rows of
+    ``qkv_rows`` at a geometry of QKV_GEOS; for QKV_CASES a permutation of M + 3 slots at any position."""
+    T, hd = case_geo(c)[3], case_geo(c)[2]
+    g = _gen(c.M + c.K)
+    bias = torch.randint(-20, 21, (c.N,), generator=g)
+    if c.geo:
+        slot, pos, S = qkv_rows(c.M, T, c.M + c.K + c.N)
+    else:
+        S = c.M + 3
+        slot = torch.randperm(S, generator=g)[:c.M].int()
+        pos = torch.randint(0, T, (c.M,), generator=g).int()
+    cos, sin = unit_rope_tables(T, hd, c.K)
+    return bias, slot, pos, S, cos, sin
+
+
+def qkv_want(proj: torch.Tensor, slot: torch.Tensor, pos: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+             geo: Geo, S: int, kv8: bool, sentinel: float = -7.0, v_only: bool = False):
+    """What one launch must leave behind, from the exact projection + bias [M, N] int64 in the kernel's row order:
+    (q [M, H hd] with ``sentinel`` on idle rows, K [S, Hkv, T_max, hd], V [S, Hkv, T_max, hd] in natural order, zero
+    wherever no row writes, owner [S, T_max]: the row that owns a cache position, -1 for none).  ``v_only``: a launch
+    of the V rows alone (q and the K cache untouched)."""
+    H, Hkv, hd, T = geo
+    M = proj.shape[0]
+    wq, wk, wv = qkv_expected(proj, pos, cos, sin, H, Hkv, hd)
+    want_q = wq.reshape(M, H * hd).clone()
+    want_q[slot < 0] = sentinel
+    if v_only:
+        want_q[:] = sentinel
+    want_k, want_v = torch.zeros(S, Hkv, T, hd), torch.zeros(S, Hkv, T, hd)
+    owner = torch.full((S, T), -1, dtype=torch.long)
+    for m in range(M):
+        sl, ps = int(slot[m]), int(pos[m])
+        if sl < 0:
+            continue
+        assert int(owner[sl, ps]) == -1, f"rows {int(owner[sl, ps])} and {m} both write (slot {sl}, position {ps})"
+        owner[sl, ps] = m
+        if not v_only:
+            want_k[sl, :, ps] = to_fp8_of_bf16(wk[m].long()) if kv8 else wk[m]
+        want_v[sl, :, ps] = to_fp8_of_bf16(wv[m].long()) if kv8 else wv[m]
+    return want_q, want_k, want_v, owner
+
+
+def qkv_mismatch(q: torch.Tensor, kn: torch.Tensor, vn: torch.Tensor, want, slot: torch.Tensor, pos: torch.Tensor,
+                 geo: Geo) -> Optional[str]:
+    """None when q [M, H hd] and the unpacked caches [S, Hkv, T_max, hd] equal ``qkv_want``'s; else a report that
+    names, per output, the count and the first mismatch's (row, head, 16-row tile, slot, position)."""
+    want_q, want_k, want_v, owner = want
+    H, Hkv, hd, _ = geo
+    out = []
+    qf = q.detach().cpu().float()
+    bad = (qf != want_q).nonzero()
+    if len(bad):
+        m, col = (int(v) for v in bad[0])
+        out.append(f"q: {len(bad)} elements differ; first at row {m} (slot {int(slot[m])}, position {int(pos[m])}), "
+                   f"head {col // hd}, tile {col // 16}, dim {col % hd}: got {float(qf[m, col])!r}, "
+                   f"want {float(want_q[m, col])!r}")
+    for name, got, w, t0 in (("K", kn, want_k, H * hd // 16), ("V", vn, want_v, (H + Hkv) * hd // 16)):
+        gf = got.detach().cpu().float()
+        bad = (gf != w).nonzero()
+        if len(bad):
+            s, h, t, d = (int(v) for v in bad[0])
+            m = int(owner[s, t])
+            out.append(f"{name} cache: {len(bad)} elements differ; first at slot {s}, kv head {h}, position {t}, dim {d} "
+                       f"(natural-order tile {t0 + (h * hd + d) // 16}; "
+                       f"{'row ' + str(m) if m >= 0 else 'no row'} writes there): got {float(gf[s, h, t, d])!r}, "
+                       f"want {float(w[s, h, t, d])!r}")
+    return "; ".join(out) if out else None
+
+
+# ---------------------------------------------------------------- the epilogue's addressing, with planted faults
+#: the planted faults of ``epi_mirror`` (module doc, "Fused QKV geometries")
+QKV_FAULTS = ("hkv", "tph", "idle", "d5", "b2")
+
+
+def _kfrag(t, d, hd: int, drop_d5: bool = False):
+    """common.h kfrag_off on tensors."""
+    blk = (t >> 4) * (hd >> 5) + (0 if drop_d5 else (d >> 5))
+    return blk * 512 + ((t & 15) + 16 * ((d & 31) >> 3)) * 8 + (d & 7)
+
+
+def _vfrag(t, d, hd: int):
+    """common.h vfrag_off on tensors."""
+    return ((t >> 5) * (hd >> 4) + (d >> 4)) * 512 + ((d & 15) + 16 * ((t & 15) >> 2)) * 8 + 4 * ((t >> 4) & 1) + (t & 3)
+
+
+def epi_mirror(acc: torch.Tensor, bias: torch.Tensor, slot: torch.Tensor, pos: torch.Tensor, cos: torch.Tensor,
+               sin: torch.Tensor, geo: Geo, S: int, kv8: bool = False, fault: Optional[str] = None,
+               sentinel: float = -7.0):
+    """A host mirror of gemm_epi.h's EPI_QKV_ROPE addressing (``epi_load_at`` + ``epi_store``): from the exact
+    accumulators acc [M, N] int64 (kernel row order) the q buffer [M, H hd] and the FRAGMENT-MAJOR caches
+    kc [S, Hkv, T_max, hd], vtc [S, Hkv, hd, T_max], walked as the kernel walks them -- per 16-row tile gt and lane
+    group lane >> 4 (4 accumulator rows nsub.., the RoPE partner rows + 8 from lane + 32).  ``fault``: None, or one of
+    QKV_FAULTS planted -- "hkv": Hkv dropped from the cache bases; "tph": tiles per head rounded down to a power of
+    two; "idle": the slot >= 0 guards dropped (an idle row writes q and, as slot 0, the caches); "d5": the d >> 5
+    term of kfrag_off dropped; "b2": the partner rows' bias taken from b1's rows.  A faulty store that leaves the
+    buffer is dropped (the mirror must not fault; the value is then missing where it belongs)."""
+    assert fault is None or fault in QKV_FAULTS
+    H, Hkv, hd, T = geo
+    M, N = acc.shape
+    bf = lambda t: t.bfloat16().float()  # noqa: E731
+    cache = (lambda t: t.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float()) if kv8 else (lambda t: t)
+    q = torch.full((M, H * hd), sentinel)
+    kc, vt = torch.zeros(S * Hkv * T * hd), torch.zeros(S * Hkv * hd * T)
+    tph = hd >> 4
+    if fault == "tph":
+        tph = 1 << (tph.bit_length() - 1)
+    qt, kt, half = H * tph, Hkv * tph, hd >> 1
+    hkv_b = 1 if fault == "hkv" else Hkv
+    rows = (torch.ones(M, dtype=torch.bool) if fault == "idle" else slot >= 0).nonzero().flatten()
+    sl, p = slot[rows].long().clamp(min=0), pos[rows].long()
+    f, b, ar4 = acc.float()[rows], bias.float(), torch.arange(4)
+
+    def store(buf, idx, val):
+        ok = (idx >= 0) & (idx < buf.numel())
+        buf[idx[ok]] = val[ok]
+
+    for gt in range(N // 16):
+        for lg in range(4):
+            nsub = lg * 4
+            n1 = gt * 16 + nsub + ar4
+            n2 = gt * 16 + ((nsub + 8) & 15) + ar4
+            b1, b2 = b[n1], b[n1 if fault == "b2" else n2]
+            if gt < qt + kt:
+                if lg >= 2:
+                    continue
+                head, it = gt // tph, gt % tph
+                j = it * 8 + nsub + ar4
+                v1, v2 = bf(f[:, n1] + b1), bf(f[:, n1 + 8] + b2)  # lane + 32 holds rows nsub + 8..
+                c, s = cos[p][:, j], sin[p][:, j]
+                y1, y2 = bf(v1 * c - v2 * s), bf(v2 * c + v1 * s)
+                if head < H:
+                    q[rows[:, None], head * hd + j] = y1
+                    q[rows[:, None], head * hd + j + half] = y2
+                else:
+                    base = ((sl * hkv_b + (head - H)) * T * hd)[:, None]
+                    store(kc, base + _kfrag(p[:, None], j[None, :], hd, fault == "d5"), cache(y1))
+                    store(kc, base + _kfrag(p[:, None], (j + half)[None, :], hd, fault == "d5"), cache(y2))
+            else:
+                vr = (gt - qt - kt) * 16 + nsub
+                kh, d = vr // hd, vr % hd
+                off = (sl * hkv_b + kh) * hd * T + _vfrag(p, d, hd)
+                store(vt, off[:, None] + ar4 * 8, cache(bf(f[:, n1] + b1)))
+    return q, kc.view(S, Hkv, T, hd), vt.view(S, Hkv, hd, T)
+
+
+def unpack_caches(kc: torch.Tensor, vt: torch.Tensor):
+    """Fragment-major caches (fp32 values) -> natural K, V [S, Hkv, T_max, hd] on the host."""
+    from cain_amd import ops
+    return ops.unpack_kcache(kc).cpu(), ops.unpack_vcache(vt).cpu()
+
+
+#: where each planted fault shows, geometry by geometry ("toy" = QKV_GEO with the rows of QKV_CASES); checked by
+#: tests/test_exact_cpu.py, which requires a report where True and silence where False
+QKV_FAULT_SHOWS = {
+    "toy": {"hkv": False, "tph": False, "idle": False, "d5": False, "b2": True},
+    "phi3": {"hkv": True, "tph": True, "idle": True, "d5": True, "b2": True},
+    "gqa": {"hkv": True, "tph": False, "idle": True, "d5": True, "b2": True},
+    "gemma": {"hkv": False, "tph": False, "idle": True, "d5": True, "b2": True},
+}
+
+
+# ---------------------------------------------------------------- row ops: quant_rows, embed, rmsnorm
+QR_CHUNK = 2048            # elements per register chunk of quant_rows_kernel: 256 threads x 8 (wgemm8.hip)
+QR_MAXK = 12 * QR_CHUNK    # 24,576
+#: one thread; exactly one chunk; one vector into chunk 1; around chunk 7; around the end of the last chunk
+QR_KS = (8, 2048, 2056, 14336, 14344, 24568, 24576)
+QR_MS = (1, 5)
+QR_REFUSED = (24584, 12)   # past QR_MAXK; no whole 8-element vectors
+E4M3_MAX = 448.0
+
+
+def e4m3_quant(y: torch.Tensor, away: bool = False) -> torch.Tensor:
+    """fp64 values -> the nearest e4m3 values (fp64), saturating at +-448, written out from the format: 3 mantissa
+    bits above 2^-6, a fixed step of 2^-9 below.  Ties go to the even code, or away from zero with ``away`` (the
+    planted wrong rounding of tests/test_rowops_exact_cpu.py)."""
+    a = y.double().abs().clamp(max=E4M3_MAX)
+    e = (torch.frexp(a)[1] - 1).clamp(min=-6)  # floor(log2 a), held at the smallest normal's exponent
+    step = torch.pow(2.0, (e - 3).double())
+    r = a / step
+    return torch.copysign((torch.floor(r + 0.5) if away else torch.round(r)) * step, y.double())
+
+
+def e4m3_bytes(v: torch.Tensor) -> torch.Tensor:
+    """Exactly representable values -> their e4m3 bytes."""
+    b = v.float().to(torch.float8_e4m3fn)
+    assert torch.equal(b.double(), v.double())
+    return b.view(torch.uint8)
+
+
+def quant_scale(x: torch.Tensor, drop_chunk: Optional[int] = None):
+    """(scale, inv) fp32 [M] of quant_rows: scale = fp32(amax / 448), 1 for a zero row; inv = fp32(1 / scale)."""
+    xf = x.float().clone()
+    if drop_chunk is not None:
+        xf[:, drop_chunk * QR_CHUNK:(drop_chunk + 1) * QR_CHUNK] = 0
+    amax = xf.abs().amax(1)
+    scale = torch.where(amax > 0, amax / torch.tensor(E4M3_MAX), torch.ones_like(amax))
+    return scale, 1.0 / scale
+
+
+def quant_rows_ref(x: torch.Tensor, norm: bool = False, eps: float = 1e-6, away: bool = False,
+                   drop_chunk: Optional[int] = None):
+    """Reference of ops.quant_rows on bf16 rows x [M, K]: (bytes uint8 [M, K], xs fp64 [M]) --
+    bytes = e4m3_rne(clamp(fp32(x) * inv, +-448)) by PyTorch's float8_e4m3fn conversion, xs = scale x
+    (rsqrt(mean x^2 + eps) in fp64 if norm else 1), scale and inv as ``quant_scale``.  Planted faults for the CPU
+    twin: ``away`` rounds ties away from zero; ``drop_chunk`` leaves one 2048-element chunk out of the row
+    statistics (amax and the sum of squares)."""
+    assert x.dtype == torch.bfloat16
+    scale, inv = quant_scale(x, drop_chunk)
+    y = (x.float() * inv[:, None]).clamp(-E4M3_MAX, E4M3_MAX)
+    b = e4m3_bytes(e4m3_quant(y, away=True)) if away else y.to(torch.float8_e4m3fn).view(torch.uint8)
+    xs = scale.double()
+    if norm:
+        xd = x.double().clone()
+        if drop_chunk is not None:
+            xd[:, drop_chunk * QR_CHUNK:(drop_chunk + 1) * QR_CHUNK] = 0
+        xs = xs * torch.rsqrt(xd.pow(2).sum(1) / x.shape[1] + eps)
+    return b, xs
+
+
+def _e4m3_specials() -> torch.Tensor:
+    """Magnitudes (fp64, <= 448, at most 8 significant bits) that a quantiser gets wrong first: every tie between
+    two e4m3 codes of each binade, to the even code below and above (17/16 -> 1, 19/16 -> 5/4, ..., 432 -> 448); the
+    subnormal range -- its codes k 2^-9, their ties (2k + 1) 2^-10 (2^-10 itself -> 0), values that vanish or round
+    up to 2^-9; the values that round up to 448."""
+    v = [(2 * n + 1) / 16.0 * 2.0 ** k for k in range(-6, 9) for n in range(8, 16)]
+    v += [(2 * k + 1) * 2.0 ** -10 for k in range(8)] + [k * 2.0 ** -9 for k in range(1, 8)]
+    v += [0.75 * 2.0 ** -10, 1.5 * 2.0 ** -10, 2.0 ** -11, 2.0 ** -12, 1.25 * 2.0 ** -9, 1.75 * 2.0 ** -9]
+    v += [446.0, 440.0, 434.0, 430.0, 416.0]  # 448 itself is planted: the row maximum, in the last vector only
+    return torch.tensor([a for a in v if a < E4M3_MAX], dtype=torch.float64)
+
+
+def quant_exact_rows(M: int, K: int, seed: int):
+    """(x bf16 [M, K], e [M]) of the exact family: row m holds y 2^e[m] with |y| <= 448 of at most 8 significant bits
+    and a planted +448 and -448 in the row's last vector (nowhere else), so amax = 448 2^e, scale = 2^e and inv = 2^-e exactly, and the bytes
+    are e4m3(y).  y: ``_e4m3_specials`` at the row's first vector, at both sides of every chunk boundary, in the last
+    vector and at random places, +-0, and m 2^k (m in 128..255, k in -16..0) elsewhere; random signs.  With five rows,
+    row 2 is all zero (+0 and -0): scale 1."""
+    g = _gen(seed)
+    y = _randint(g, 128, 255, (M, K)).double() * torch.pow(2.0, _randint(g, -16, 0, (M, K)).double())
+    y[torch.rand(M, K, generator=g) < 1.0 / 16] = 0.0
+    sp = _e4m3_specials()
+    edges = [k for c in range(1, -(-K // QR_CHUNK)) for k in (c * QR_CHUNK - 1, c * QR_CHUNK)]
+    e = torch.empty(M, dtype=torch.long)
+    for m in range(M):
+        where = list(range(min(8, K))) + edges + list(range(max(K - 8, 0), K))
+        where += torch.randint(0, K, (min(K, 3 * len(sp)),), generator=g).tolist()
+        where = torch.tensor(where)
+        y[m, where] = sp[(torch.arange(len(where)) + 7 * m + seed) % len(sp)]
+    y = y * (_randint(g, 0, 1, (M, K)) * 2 - 1).double()  # signs, of the zeros too
+    for m in range(M):
+        e[m] = (seed + 3 * m) % 10 - 6  # -6..3
+        y[m, K - 1 - (seed + m) % 8] = E4M3_MAX if (seed + m) % 2 else -E4M3_MAX
+        y[m, K - 1 - (seed + m + 3) % 8] = -E4M3_MAX if (seed + m) % 2 else E4M3_MAX
+    x = y * torch.pow(2.0, e.double())[:, None]
+    if M == 5:
+        x[2] = torch.where(torch.rand(K, generator=g) < 0.5, 0.0, -0.0).double()
+    xb = x.bfloat16()
+    assert torch.equal(xb.double(), x), "the exact family must be exact in bf16"
+    return xb, e
+
+
+def quant_general_rows(M: int, K: int, seed: int) -> torch.Tensor:
+    """Random bf16 rows, 3 x randn: amax is no power of two, so scale and inv round."""
+    return (3.0 * torch.randn(M, K, generator=_gen(seed))).bfloat16()
+
+
+def quant_norm_rows(M: int, K: int, seed: int) -> torch.Tensor:
+    """Sparse integer rows for the folded RMSNorm factor: min(16, K) non-zeros in +-1..+-4 per row, so the sum of
+    squares (<= 256) is an exact integer in fp32 in any order.  They sit at the row's first and last element, in
+    each of the four waves' ranges of one chunk (elements 512 w.. of it) and on both sides of chunk boundaries --
+    the last boundary always, the others in turn over the rows; the rest at random places."""
+    g = _gen(seed)
+    x = torch.zeros(M, K, dtype=torch.float64)
+    nchunk = -(-K // QR_CHUNK)
+    for m in range(M):
+        where = [0, K - 1]
+        c0 = (m + seed) % nchunk
+        where += [k for w in range(4) for k in (c0 * QR_CHUNK + 512 * w + int(torch.randint(0, 512, (1,), generator=g)),)
+                  if k < K]
+        bounds = [nchunk - 1] + [1 + (m + seed + i) % max(1, nchunk - 1) for i in range(nchunk)]
+        for c in bounds:
+            if 0 < c < nchunk:
+                where += [c * QR_CHUNK - 1, c * QR_CHUNK]
+        where = list(dict.fromkeys(where))[:16]
+        for k in torch.randperm(K, generator=g).tolist():
+            if len(where) >= min(16, K):
+                break
+            if k not in where:
+                where.append(k)
+        val = _randint(g, 1, 4, (len(where),)) * (_randint(g, 0, 1, (len(where),)) * 2 - 1)
+        x[m, torch.tensor(where)] = val.double()
+    return x.bfloat16()
+
+
+def _e4m3_code(b: torch.Tensor) -> torch.Tensor:
+    """e4m3 bytes -> signed code numbers (adjacent values differ by 1; +0 and -0 are both 0)."""
+    i = b.to(torch.int32)
+    return torch.where(i >= 128, -(i & 127), i)
+
+
+def quant_exact_mismatch(x: torch.Tensor, got8: torch.Tensor, gotxs: torch.Tensor) -> Optional[str]:
+    """The exact family's comparator: bytes and (un-normed) scales equal to ``quant_rows_ref`` bit for bit."""
+    ref8, refxs = quant_rows_ref(x)
+    rep = mismatches(got8.cpu().to(torch.int32), ref8.to(torch.int32))
+    if rep is not None:
+        c = int((got8.cpu() != ref8).nonzero()[0][1])
+        return f"bytes (chunk {c // QR_CHUNK}, thread {c % QR_CHUNK // 8}): {rep}"
+    rep = mismatches(gotxs.cpu().double()[:, None], refxs[:, None])
+    return None if rep is None else f"scale: {rep}"
+
+
+def quant_general_mismatch(x: torch.Tensor, got8: torch.Tensor, gotxs: torch.Tensor):
+    """The general family's comparator: (number of bytes that differ from the reference's, report or None).  Per
+    element |e4m3(x8) scale - x| <= max(2^-4 |y|, 2^-10) scale (1 + 2^-20) with y = x inv -- half an e4m3 step,
+    normal or subnormal, with a margin for the two fp32 roundings of scale and inv; the bytes at most one code from
+    the reference's; the scale the reference's bit for bit (amax / 448 is one correctly rounded fp32 division)."""
+    ref8, refxs = quant_rows_ref(x)
+    scale, inv = quant_scale(x)
+    g8 = got8.cpu()
+    ndiff = int((g8 != ref8).sum())
+    rep = mismatches(gotxs.cpu().double()[:, None], refxs[:, None])
+    if rep is not None:
+        return ndiff, f"scale: {rep}"
+    y = x.double() * inv.double()[:, None]
+    s = scale.double()[:, None]
+    deq = g8.view(torch.float8_e4m3fn).double() * s
+    over = (deq - x.double()).abs() - torch.maximum(2.0 ** -4 * y.abs(), torch.tensor(2.0 ** -10, dtype=torch.float64)) \
+        * s * (1 + 2.0 ** -20)
+    over = torch.where(over.isnan(), torch.tensor(float("inf"), dtype=torch.float64), over)  # an e4m3 NaN byte
+    if float(over.max()) > 0:
+        r, c = divmod(int(over.argmax()), x.shape[1])
+        return ndiff, (f"{int((over > 0).sum())} elements past half an e4m3 step; worst at row {r}, column {c} (chunk "
+                       f"{c // QR_CHUNK}): x {float(x[r, c])!r}, byte {int(g8[r, c]):#04x}, reference {int(ref8[r, c]):#04x}")
+    far = (_e4m3_code(g8) - _e4m3_code(ref8)).abs() > 1
+    if bool(far.any()):
+        r, c = (int(v) for v in far.nonzero()[0])
+        return ndiff, f"row {r}, column {c}: byte {int(g8[r, c]):#04x} is more than one code from {int(ref8[r, c]):#04x}"
+    return ndiff, None
+
+
+QR_NORM_RTOL = 2.0 ** -21  # 8 fp32 ulp: rms_inv is one v_rcp_f32 and one v_rsq_f32 (~1 ulp each) + 3 roundings
+
+
+def quant_norm_mismatch(x: torch.Tensor, gotxs: torch.Tensor, eps: float) -> Optional[str]:
+    """xs with the RMSNorm factor folded in, against the fp64 reference to a relative 2^-21."""
+    _, refxs = quant_rows_ref(x, norm=True, eps=eps)
+    rel = (gotxs.cpu().double() - refxs).abs() / refxs
+    r = int(rel.argmax())
+    if not float(rel[r]) <= QR_NORM_RTOL:
+        return f"row {r}: xs {float(gotxs[r])!r}, want {float(refxs[r])!r}: off by {float(rel[r]) * 2 ** 24:.2f} x 2^-24"
+    return None
+
+
+EMBED_DS = (8, 2040, 2048, 2056, 3584)  # one vector; one short of / exactly / one past a full round of 256 threads
+EMBED_MS = (1, 300)
+NORM_DS = (8, 2048, 8192, 8200, 16384)  # 8200 and 16384 run rmsnorm_kernel<512>; 8200 leaves its second round partial
+NORM_REFUSED = (16392, 12)
+
+
+def embed_scales(d: int):
+    """1 (a copy) and sqrt(d) rounded to bf16, as the engine passes for Gemma."""
+    return 1.0, float(torch.tensor(float(d)).sqrt().bfloat16())
+
+
+def embed_case(M: int, d: int, seed: int, rows: int = 37):
+    """(table bf16 [rows, d], finite: randn over 14 binades; tok int32 [M]: row 0 first, the last row second when
+    M > 1 and last, repeats in between)."""
+    g = _gen(seed)
+    E = (torch.randn(rows, d, generator=g) * torch.pow(2.0, _randint(g, -10, 3, (rows, d)).float())).bfloat16()
+    assert bool(E.float().isfinite().all())
+    tok = torch.randint(0, rows, (M,), generator=g).int()
+    tok[0] = 0
+    if M > 1:
+        tok[1] = tok[-1] = rows - 1
+        tok[M // 2] = tok[M // 2 - 1]
+    return E, tok
+
+
+def embed_ref(E: torch.Tensor, tok: torch.Tensor, scale: float) -> torch.Tensor:
+    """bf16(fp32(E[tok]) x scale): one fp32 product, one round-to-nearest-even."""
+    return (E[tok.long()].float() * scale).bfloat16()
+
+
+def bits16(t: torch.Tensor) -> torch.Tensor:
+    """bf16 -> its 16 bits as int32 (so that -0 and +0 differ)."""
+    return t.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+
+
+def bf16_ord(t: torch.Tensor) -> torch.Tensor:
+    """bf16 -> integers in value order: adjacent bf16 numbers differ by 1 (+0 and -0 are both 0)."""
+    i = bits16(t)
+    return torch.where(i >= 0x8000, -(i & 0x7FFF), i)
+
+
+def rmsnorm_case(M: int, d: int, seed: int):
+    """(x bf16 [M, d] of integers -16..16: the sum of squares is below 16384 x 256 = 2^22, exact in fp32 in any order;
+    gain bf16 [d], randn)."""
+    g = _gen(seed)
+    return _randint(g, -16, 16, (M, d)).to(torch.bfloat16), torch.randn(d, generator=g).bfloat16()
+
+
+def rmsnorm_ref(x: torch.Tensor, gain: torch.Tensor, eps: float) -> torch.Tensor:
+    """bf16(bf16(x inv) g) with inv = rsqrt(mean x^2 + eps) in fp64."""
+    xd = x.double()
+    inv = torch.rsqrt(xd.pow(2).mean(-1, keepdim=True) + eps)
+    return ((xd * inv).bfloat16().double() * gain.double()).bfloat16()
+
+
+def rmsnorm_mismatch(got: torch.Tensor, x: torch.Tensor, gain: torch.Tensor, eps: float):
+    """(number of elements that differ from ``rmsnorm_ref`` at all, report or None): every output within one bf16
+    step of the reference (the kernel's inv, ~8 fp32 ulp from the fp64 one, may flip a rounding)."""
+    ref = rmsnorm_ref(x, gain, eps)
+    steps = (bf16_ord(got.cpu()) - bf16_ord(ref)).abs()
+    steps = torch.where(got.cpu().float().isfinite(), steps, torch.full_like(steps, 1 << 16))
+    ndiff = int((steps > 0).sum())
+    if int(steps.max()) > 1:
+        r, c = (int(v) for v in (steps > 1).nonzero()[0])
+        return ndiff, (f"{int((steps > 1).sum())} elements more than one bf16 step off; first at row {r}, column {c} "
+                       f"(vector {c // 8}): got {float(got[r, c])!r}, want {float(ref[r, c])!r}")
+    return ndiff, None
 
 
 if __name__ == "__main__":  # regenerate TILE_FLOORS

@@ -164,3 +164,74 @@ def test_tile_floors_are_current():
     for fam, kind in exact.soft_keys():
         got = exact.measure_floor(fam, kind)
         assert abs(got - exact.TILE_FLOORS[f"{fam}/{kind}"]) <= 1e-3 * got, (fam, kind, got)
+
+
+# ---------------------------------------------------------------- fused QKV at the models' geometries
+@pytest.mark.parametrize("c", exact.QKV_GEO_CASES, ids=lambda c: c.id)
+def test_every_geometry_case_is_inside_the_exactness_bounds(c):
+    """As above for ``QKV_GEO_CASES`` (``exact.product`` asserts each bound), and the rows of the launch are what the
+    GPU test relies on: idle first and last rows, a shared slot across the block edges, one owner per write."""
+    H, Hkv, hd, T = exact.case_geo(c)
+    assert c.N == (H + 2 * Hkv) * hd and c.M == exact.QKV_GEO_ROWS[c.fam, c.K]
+    x, ew, ref = exact.case_inputs(c)
+    assert torch.equal(x.to(torch.bfloat16).long(), x)
+    if c.fam in ("w8a8", "w4a8"):
+        plant = exact.a8_plant(c)
+        assert bool((x.abs().amax(1) == plant).all())
+        x8 = x.float() * (448 // plant)
+        assert torch.equal(x8.to(torch.float8_e4m3fn).float(), x8)
+    if c.fam in ("w4", "w4a8"):
+        assert int((x % 2).abs().max()) == 0
+    if c.fam == "bf16" and c.M > 64:
+        for ks in (2, 3, 4, 8):
+            exact.assert_fp16_slabs(x, ew, ks)
+    bias, slot, pos, S, cos, sin = exact.qkv_launch(c)
+    if c.tag == "qkv8":
+        assert int(ref.abs().max()) + 20 <= 448  # |k|, |v| <= 448 with the integer bias: no e4m3 saturation
+    idle = slot < 0
+    assert bool(idle[0]) and bool(idle[-1]) and c.M // 5 <= int(idle.sum()) <= c.M // 3 and bool((pos[idle] == 0).all())
+    assert int(slot.max()) < S and 0 <= int(pos.min()) and int(pos.max()) == T - 1
+    pairs = [(int(s), int(p)) for s, p in zip(slot, pos) if s >= 0]
+    assert len(set(pairs)) == len(pairs)
+    by_slot = {}
+    for s, p in pairs:
+        by_slot.setdefault(s, set()).add(p)
+    assert any({15, 16, 31, 32, T - 1} <= ps for ps in by_slot.values())
+    assert T % 32 == 0 and T & (T - 1)  # whole blocks, no power of two
+
+
+def _mirror_report(c, fault):
+    x, ew, ref = exact.case_inputs(c)
+    geo = exact.case_geo(c)
+    bias, slot, pos, S, cos, sin = exact.qkv_launch(c)
+    kv8 = c.tag == "qkv8"
+    want = exact.qkv_want(ref + bias, slot, pos, cos, sin, geo, S, kv8)
+    q, kc, vt = exact.epi_mirror(ref, bias, slot, pos, cos, sin, geo, S, kv8, fault)
+    kn, vn = exact.unpack_caches(kc, vt)
+    return exact.qkv_mismatch(q, kn, vn, want, slot, pos, geo)
+
+
+MIRROR_CASES = {"toy": [exact.qkv_case("w8", 1088, 5, kv8) for kv8 in (False, True)],
+                **{geo: [exact.qkv_case("w8", 1088, 40, kv8, geo) for kv8 in (False, True)] for geo in exact.QKV_GEOS}}
+
+
+@pytest.mark.parametrize("geo", list(MIRROR_CASES))
+def test_epilogue_mirror_agrees_and_planted_faults_are_caught(geo):
+    """The fault-free mirror of the epilogue's addressing leaves exactly what ``qkv_want`` expects (two independent
+    statements of the epilogue: one by addresses, one by values); each planted fault is reported at every geometry
+    where it can show and at no other -- ``exact.QKV_FAULT_SHOWS``: at the 2 / 1 / 32 geometry "hkv", "tph", "idle"
+    and "d5" are invisible."""
+    for c in MIRROR_CASES[geo]:
+        assert _mirror_report(c, None) is None
+        for fault in exact.QKV_FAULTS:
+            rep = _mirror_report(c, fault)
+            print(geo, c.tag, fault, rep)
+            assert (rep is not None) == exact.QKV_FAULT_SHOWS[geo][fault], (geo, c.tag, fault, rep)
+            if rep is not None:
+                assert "slot" in rep and "position" in rep and ("row" in rep) and ("head" in rep)
+
+
+def test_an_idle_row_fault_names_the_row():
+    c = MIRROR_CASES["gqa"][0]
+    rep = _mirror_report(c, "idle")
+    assert rep.startswith("q:") and "first at row 0 (slot -1, position 0)" in rep

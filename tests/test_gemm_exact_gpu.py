@@ -2,7 +2,11 @@
 it bit for bit, bf16 outputs equal its round-to-nearest-even, the fused QKV + RoPE + KV-append epilogue is a signed
 permutation of it, on each forced kernel path (confirmed through the library's own query functions), twice per
 path (tickets and counters reset).  A failure names the (row, 16-column tile).  Fused RMSNorm and the SiLU / GeLU
-epilogues, which cannot be exact, are held to 3 x the per-tile rounding floor of their output type."""
+epilogues, which cannot be exact, are held to 3 x the per-tile rounding floor of their output type.
+
+The fused QKV epilogue runs at the 2 / 1 / 32 head geometry on every path and row count (``exact.QKV_CASES``), and at
+phi3's, a GQA and gemma's head shape with idle rows and shared slots (``exact.QKV_GEO_CASES``): there every family and
+both cache types at one row count each, none left out; a failure names (row, head, tile, slot, position)."""
 import sys
 from pathlib import Path
 
@@ -285,16 +289,16 @@ def test_w4a8_split_k_within_fp16_slab_rounding(c):
 
 
 # ---------------------------------------------------------------- fused QKV + RoPE + KV append
-def _qkv(c: Case, kv8: bool, tile0_v: bool = False):
-    H, Hkv, hd, T = exact.QKV_H, exact.QKV_HKV, exact.QKV_HD, exact.QKV_TMAX
+def _qkv(c: Case, kv8: bool, tile0_v: bool = False, geo=None):
+    """One fused-QKV case, twice: q, both caches and everything no row owns (idle rows' q, the rest of the caches)
+    against ``exact.qkv_want``; a failure names (row, head, tile, slot, position)."""
+    geo = exact.case_geo(c) if geo is None else geo
+    H, Hkv, hd, T = geo
+    assert c.N == exact.qkv_n(geo)
     x, ew, ref = exact.case_inputs(c)  # weight rows in the kernel's order (random rows: any order is a valid case)
-    M, S = c.M, c.M + 3
-    g = torch.Generator().manual_seed(c.M + c.K)
-    bias = torch.randint(-20, 21, (c.N,), generator=g)
-    slot = torch.randperm(S, generator=g)[:M].int()
-    pos = torch.randint(0, T, (M,), generator=g).int()
-    cos, sin = exact.unit_rope_tables(T, hd, c.K)
-    wq, wk, wv = exact.qkv_expected(ref + bias, pos, cos, sin, H, Hkv, hd)
+    M = c.M
+    bias, slot, pos, S, cos, sin = exact.qkv_launch(c)
+    want = exact.qkv_want(ref + bias, slot, pos, cos, sin, geo, S, kv8, sentinel=-7.0, v_only=bool(tile0_v))
     p, xd = dev(ew.packed), x.to(torch.bfloat16).to(DEV)
     cdt = torch.uint8 if kv8 else torch.bfloat16
     for rep in range(2):
@@ -314,18 +318,9 @@ def _qkv(c: Case, kv8: bool, tile0_v: bool = False):
             run(c.fam, p, xd, c.N, QKV, bias=b, out=q, rope=rope)
         kf = kc.view(torch.float8_e4m3fn).float() if kv8 else kc.float()
         vf = vt.view(torch.float8_e4m3fn).float() if kv8 else vt.float()
-        kn, vn = ops.unpack_kcache(kf).cpu(), ops.unpack_vcache(vf).cpu()
-        want_k, want_v = torch.zeros_like(kn), torch.zeros_like(vn)
-        for m in range(M):  # every appended (slot, pos); everything else must still be zero
-            sl, ps = int(slot[m]), int(pos[m])
-            if not tile0_v:
-                want_k[sl, :, ps] = exact.to_fp8_of_bf16(wk[m].long()) if kv8 else wk[m]
-            want_v[sl, :, ps] = exact.to_fp8_of_bf16(wv[m].long()) if kv8 else wv[m]
-        tag = f"{c.id} run {rep}"
-        exact.assert_equal(kn.reshape(-1, hd), want_k.reshape(-1, hd), tag + " K cache [slot x head x pos, hd]")
-        exact.assert_equal(vn.reshape(-1, hd), want_v.reshape(-1, hd), tag + " V cache [slot x head x pos, hd]")
-        want_q = torch.full_like(q.cpu().float(), -7.0) if tile0_v else wq.reshape(M, H * hd)
-        exact.assert_equal(q.float(), want_q, tag + " q")
+        kn, vn = exact.unpack_caches(kf, vf)
+        report = exact.qkv_mismatch(q, kn, vn, want, slot, pos, geo)
+        assert report is None, f"{c.id} run {rep}: {report}"
 
 
 @pytest.mark.parametrize("c", exact.QKV_CASES, ids=ids)
@@ -343,6 +338,60 @@ def test_qkv_rope_is_a_signed_permutation(c):
         assert ops.w8a8_eligible(c.N, c.K, c.M)
         _a8_quant(c, exact.case_inputs(c)[0])
     _qkv(c, c.tag == "qkv8")
+
+
+@pytest.mark.parametrize("c", exact.QKV_GEO_CASES, ids=ids)
+def test_qkv_rope_at_the_models_geometries(c):
+    """Every family's epilogue at phi3's, a GQA and gemma's head shape (``exact.QKV_GEOS``: 6 tiles per head, Hkv > 1,
+    hd >> 5 up to 8, T_max = 96), with idle rows whose q must keep its sentinel and who add nothing to either cache,
+    and rows sharing a slot at positions 15 / 16, 31 / 32 and T_max - 1 (``exact.qkv_rows``).  The bias stays in the
+    kernel's row order, so b1 / b2 are checked per head.  One row count per family, across its row-block or launch
+    boundary (``exact.QKV_GEO_ROWS``); no family is left out of any geometry."""
+    if c.fam in ("q4_0", "q4_k", "q6"):
+        rows = q_rows(c.fam, c.K, QKV)
+        assert rows == exact.QKV_ROWS[c.K] and c.M == 2 * rows + 1
+    if c.fam == "bf16" and c.M > 64:
+        assert ops.wide_gemm_eligible(c.N, c.K, c.M)
+        ks, variant = ops.wide_gemm_plan(c.N, c.K, c.M)
+        if variant == 0:
+            x, ew, _ = exact.case_inputs(c)
+            exact.assert_fp16_slabs(x, ew, ks)
+    elif c.fam == "bf16":
+        assert (ops.gemm_ws_bytes(c.N, c.K, c.M) > 0) == (c.M > 16)  # batched above 16 rows, else the skinny kernel
+    if c.fam in A8:
+        assert ops.w8a8_eligible(c.N, c.K, c.M) and c.M > 128  # the 256-row tile
+        _a8_quant(c, exact.case_inputs(c)[0])
+    _qkv(c, c.tag == "qkv8")
+
+
+#: one family per entry file: gemm.hip, gemm_w8.hip, gemm_w4.hip, gemm_qstream.hip, wgemm8.hip
+REFUSED = [("bf16", 1056, 16), ("w8", 1088, 5), ("w4", 1920, 5), ("q6", 3072, 4), ("w8a8", 640, 40)]
+
+
+@pytest.mark.parametrize("hd", [40, 24])
+@pytest.mark.parametrize("fam,K,M", REFUSED, ids=lambda v: str(v))
+def test_qkv_rope_refuses_head_sizes_it_cannot_tile(fam, K, M, hd):
+    """hd = 40 ((hd / 2) % 8 != 0) and hd = 24 (hd % 16 != 0): ``gemm_args`` refuses, the entry returns an error
+    before any launch of its own, and nothing is written (W8A8: ``quant_rows`` has run by then, into its own
+    buffers)."""
+    H, Hkv, T = 2, 2, 64
+    N = (H + 2 * Hkv) * hd  # 240, 144: whole 16-row tiles
+    ew = exact.GENERATORS[fam](N, K, 1)
+    p = dev(ew.packed)
+    xd = exact.int_x(M, K, 2, plant=exact.a8_plant(Case(fam, N, K, M))).to(torch.bfloat16).to(DEV)
+    kc = torch.zeros(M, Hkv, T, hd, device=DEV, dtype=torch.bfloat16)
+    vt = torch.zeros(M, Hkv, hd, T, device=DEV, dtype=torch.bfloat16)
+    q = torch.full((M, H * hd), -7.0, device=DEV).bfloat16()
+    cos, sin = exact.unit_rope_tables(T, hd, 3)
+    rope = dict(kc=kc, vtc=vt, slot=torch.arange(M, dtype=torch.int32, device=DEV),
+                pos=torch.zeros(M, dtype=torch.int32, device=DEV), cos_t=cos.to(DEV), sin_t=sin.to(DEV), H=H, Hkv=Hkv,
+                hd=hd)
+    with pytest.raises(RuntimeError, match=r"failed \(rc="):
+        if fam == "bf16":
+            ops.qkv_rope(p["wp"], xd, N, q, kc, vt, rope["slot"], rope["pos"], rope["cos_t"], rope["sin_t"], H, Hkv, hd)
+        else:
+            run(fam, p, xd, N, QKV, out=q, rope=rope)
+    assert bool((q == -7.0).all()) and int(kc.count_nonzero()) == 0 and int(vt.count_nonzero()) == 0
 
 
 @pytest.mark.parametrize("M", [4, 9])
