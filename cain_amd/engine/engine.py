@@ -41,7 +41,7 @@ import torch
 from ..models.config import ModelConfig, get_config, rope_inv_freq
 from ..models.hf import checkpoint_for, load_hf_weights, load_pretrained, load_tokenizer
 from ..models.tokenizer import get_tokenizer
-from . import jsonmode
+from . import jsonmode, stopseq
 from .speculative import K_MAX, SeqState, draft_model_given, draft_model_rows, draft_token, dvalid_after
 from .speculative import draft as spec_draft_host
 from ..models.weights import WEIGHT_DTYPES, ModelWeights, pack_for_engine, random_weights, roundtrip_weights
@@ -89,6 +89,9 @@ class GenResult:
     # "open" -- the budget ran out inside the document (the text is a viable prefix); "fail" -- the sampler drew a
     # masked token (a rounding of its last prefix sum), which was taken back
     json_state: Optional[str] = None
+    # stop sequences (options.stop): the string that ended the row (None: the row had none, or hit none); the text
+    # is then cut where that occurrence starts, ``tokens`` keeps every generated token
+    stop_hit: Optional[str] = None
 
     @property
     def prompt_eval_count(self) -> int:
@@ -140,6 +143,8 @@ def _row_options(opts: Optional[Dict], cfg: ModelConfig, index: int, base_seed: 
                 # eos_id -1 disables every stop)
                 stop=tuple(int(x) for x in (opts["stop_ids"] if opts and "stop_ids" in opts else
                                             () if opts and "eos_id" in opts else cfg.stop_ids))[:3],
+                # stop strings (options.stop, engine/stopseq.py) under a name of their own: ``stop`` above is the ids
+                stop_strs=stopseq.parse_stop(opts.get("stop")) if opts else (),
                 seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
 
 
@@ -373,6 +378,10 @@ def taken_record(record: Sequence[int], n: int, prompt: Sequence[int]) -> List[i
     return list(record[:n]) + [int(t) for t in prompt[n:len(prompt) - 1]]
 
 
+SPEC_STOP_REFUSAL = ("stop strings cannot be combined with speculative decoding (one step commits several tokens; "
+                     "token ids go in stop_ids)")
+
+
 class _PieceDecoder:
     """``decode`` by the byte pieces of ``DecodeEngine.set_json_vocab`` (a character cut at the end decodes to
     U+FFFD, which ``StreamDecoder`` holds back)."""
@@ -448,6 +457,9 @@ class DecodeEngine:
         self._json_custom = False  # ... given by set_json_vocab: the text of a JSON row is spelt with it
         self._gr: Optional[Dict] = None  # JSON mode's device buffers (hip backend), made at first use (_gr_bufs)
         self._last_json: Optional[List[Optional[str]]] = None
+        self._pieces: Optional[List[bytes]] = None  # the tokenizer's byte pieces, made at first use (_piece_vocab)
+        self._st: Optional[Dict] = None  # the stop sequences' device buffers (hip backend), made at first use
+        self._last_stop: Optional[List[Optional[tuple]]] = None  # per row of the last generate: (hit_start, index)
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
         if weight_dtype == "fp4" and any(k % 128 for k in (self.cfg.d_model, self.cfg.q_dim, self.cfg.ffn)):
@@ -774,25 +786,84 @@ class DecodeEngine:
         jsonmode.check_vocabulary(pieces)
         with self._json_lock:
             self._json_pieces, self._json_custom = pieces, True
-        self._gr = None
-        for key in [k for k in getattr(self, "_graphs", {}) if "gr" in k]:  # graphs that captured the old table
+        self._gr = self._st = None
+        for key in [k for k in getattr(self, "_graphs", {}) if "gr" in k or "st" in k]:  # ... captured the old table
             self.lib.cain_graph_destroy(ctypes.c_void_p(self._graphs.pop(key)))
 
     def _json_vocab(self) -> List[bytes]:
         with self._json_lock:  # (a server's handler threads and its scheduler thread may both ask first)
             if self._json_pieces is None:
-                pieces = jsonmode.token_bytes(self.tokenizer, self.cfg.vocab)
+                pieces = self._pieces or jsonmode.token_bytes(self.tokenizer, self.cfg.vocab)
                 jsonmode.check_vocabulary(pieces)
-                self._json_pieces = pieces
+                self._json_pieces = self._pieces = pieces
             return self._json_pieces
+
+    def _piece_vocab(self) -> List[bytes]:
+        """The bytes each token id appends to a row's stream, for the stop sequences: ``set_json_vocab``'s pieces when
+        given, else the tokenizer's own -- JSON mode's table without its ``check_vocabulary``, which only JSON needs."""
+        with self._json_lock:
+            if self._json_custom:
+                return self._json_pieces
+            if self._pieces is None:
+                self._pieces = jsonmode.token_bytes(self.tokenizer, self.cfg.vocab)
+            return self._pieces
 
     def _json_text(self, toks: Sequence[int]) -> str:
         return b"".join(self._json_pieces[t] for t in toks).decode("utf-8", errors="replace")
 
-    def text_decoder(self, json_row: bool = False):
-        """What turns a row's token ids into text (``.decode(ids)``): the tokenizer, or -- for a JSON-mode row of an
-        engine whose vocabulary ``set_json_vocab`` supplied -- that vocabulary's bytes."""
-        return _PieceDecoder(self) if json_row and self._json_custom else self.tokenizer
+    def text_decoder(self, json_row: bool = False, stop_row: bool = False):
+        """What turns a row's token ids into text (``.decode(ids)``): the tokenizer, or -- for a JSON-mode row or a
+        row with stop strings of an engine whose vocabulary ``set_json_vocab`` supplied -- that vocabulary's bytes."""
+        return _PieceDecoder(self) if (json_row or stop_row) and self._json_custom else self.tokenizer
+
+    def stop_cut(self, toks: Sequence[int], text: str, hit_start: int) -> str:
+        """``text`` (the decoder's text of all of ``toks``) of a row whose stop string starts at byte ``hit_start`` of
+        its stream, cut there (engine/stopseq.py ``cut_text``)."""
+        pieces = self._piece_vocab()
+        return stopseq.cut_text(text, b"".join(pieces[t] if 0 <= t < len(pieces) else b"" for t in toks), hit_start)
+
+    # ---------------------------------------------------------------- stop sequences
+    def _st_bufs(self) -> Dict:
+        """Device buffers of the stop sequences (csrc/stopseq.hip): per decode row the flag, the match state and the
+        strings, and the vocabulary's piece table (JSON mode's tensors when it has made them: the same pieces)."""
+        if self._st is None:
+            from .. import ops
+
+            R, dev = self.gen.shape[0], self.device
+            pieces = self._piece_vocab()
+            table = {k: self._gr[k] for k in ("V", "piece_off", "piece_bytes")} if self._gr is not None \
+                else ops.json_table(pieces, dev)
+            on, ln, by = ops.stop_table([()] * R, dev)
+            self._st = dict(table, stop_on=on, stop_len=ln, stop_bytes=by,
+                            sstate=ops.stop_states([stopseq.INITIAL] * R, dev))
+        return self._st
+
+    def _st_struct(self):
+        from .. import ops
+
+        b, q = self._st_bufs(), ops.CainStop()
+        q.stop_on, q.sstate, q.stop_len, q.stop_bytes = (_ptr(b["stop_on"]), _ptr(b["sstate"]), _ptr(b["stop_len"]),
+                                                         _ptr(b["stop_bytes"]))
+        q.piece_off, q.piece_bytes = _ptr(b["piece_off"]), _ptr(b["piece_bytes"])
+        return q
+
+    def _st_begin(self, rows: slice, stops: Sequence[Sequence[str]]) -> None:
+        """Decode rows ``rows`` start requests: their stop strings, every state at the start of a stream."""
+        from .. import ops
+
+        b = self._st_bufs()
+        on, ln, by = ops.stop_table_host(stops)
+        b["stop_on"][rows].copy_(on)
+        b["stop_len"][rows].copy_(ln)
+        b["stop_bytes"][rows].copy_(by)
+        b["sstate"][rows].copy_(ops.stop_states([stopseq.INITIAL] * len(stops), "cpu"))
+
+    def _st_hits(self, n: int, stops: Sequence[Sequence[str]]) -> List[Optional[tuple]]:
+        """Per decode row ``0 .. n - 1``: ``(hit_start, index)`` of the stop string that ended it, or None."""
+        from .. import ops
+
+        st = ops.stop_states_host(self._st_bufs()["sstate"][:n])
+        return [(s[3], s[4]) if stops[i] and s[3] >= 0 else None for i, s in enumerate(st)]
 
     def _gr_bufs(self) -> Dict:
         """Device buffers of JSON mode (csrc/grammar.hip): per decode row the mode flag and the automaton state, and
@@ -828,12 +899,19 @@ class DecodeEngine:
         return [names.get(jsonmode.sid_of(s), "open") if f else None for s, f in zip(st, fmt)]
 
     def _forward(self, M: int, rows, want_logits: bool, want_sample: bool, lp: Optional[_CainLogprob] = None,
-                 gr=None) -> None:
+                 gr=None, st=None) -> None:
         rs = self._rows_struct(rows, want_sample)
         plan = self._plan(M)
         _set_cu_budget(self.lib, self.cu_limit)  # launch sizing for this engine's stream (0: whole device)
         try:
-            if gr is not None:
+            if st is not None:
+                from .. import ops
+
+                rc = ops.load_stop().cain_plan_forward_st(
+                    ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits), int(want_sample),
+                    ctypes.byref(lp) if lp is not None else None, ctypes.byref(gr) if gr is not None else None,
+                    ctypes.byref(st), ctypes.c_void_p(self.stream.cuda_stream))
+            elif gr is not None:
                 from .. import ops
 
                 rc = ops.load_grammar().cain_plan_forward_gr(
@@ -853,11 +931,12 @@ class DecodeEngine:
             where = self.lib.cain_plan_last_failure()
             raise RuntimeError(f"cain_plan_forward failed rc={rc}" + (f" at {where.decode()}" if where else ""))
 
-    def _graph(self, M: int, steps: int, lp: bool = False, gr: bool = False) -> int:
+    def _graph(self, M: int, steps: int, lp: bool = False, gr: bool = False, st: bool = False) -> int:
         """``lp``: the steps also compute token log-probabilities (for the rows whose ``topn`` says so when the graph
         runs) -- a cache entry of its own; without it the graph is launch for launch the one it always was.
-        ``gr``: the steps run JSON mode's mask and advance (for the rows whose ``gram_on`` says so), likewise."""
-        key = (M, steps) + (("lp",) if lp else ()) + (("gr",) if gr else ())
+        ``gr``: the steps run JSON mode's mask and advance (for the rows whose ``gram_on`` says so), likewise.
+        ``st``: the steps match the stop sequences (for the rows whose ``stop_on`` says so), likewise."""
+        key = (M, steps) + (("lp",) if lp else ()) + (("gr",) if gr else ()) + (("st",) if st else ())
         g = self._graphs.get(key)
         if g is None:
             rs = self._rows_struct(self.rows, True)
@@ -865,7 +944,16 @@ class DecodeEngine:
             plan = self._plan(M)
             _set_cu_budget(self.lib, self.cu_limit)
             try:
-                if gr:
+                if st:
+                    from .. import ops
+
+                    q, gs, ss = (self._lp_struct(True) if lp else None), (self._gr_struct() if gr else None), \
+                        self._st_struct()
+                    g = ops.load_stop().cain_plan_capture_st(
+                        ctypes.c_void_p(plan), M, ctypes.byref(rs), steps, ctypes.byref(q) if lp else None,
+                        ctypes.byref(gs) if gr else None, ctypes.byref(ss), ctypes.c_void_p(self.stream.cuda_stream),
+                        ctypes.byref(err))
+                elif gr:
                     from .. import ops
 
                     q, gs = (self._lp_struct(True) if lp else None), self._gr_struct()
@@ -1055,7 +1143,12 @@ class DecodeEngine:
         whose top-level value is an object (engine/jsonmode.py; on the HIP backend a mask on the logits inside the
         decode graphs, csrc/grammar.hip).  The row ends on the token that closes the object (``done_reason`` "stop",
         no EOS needed); a row whose budget runs out first holds a viable prefix ("length").  The state starts fresh
-        per request; the prompt is not constrained.  Not together with speculative decoding."""
+        per request; the prompt is not constrained.  Not together with speculative decoding.
+        ``options["stop"]`` (a string or up to 8 strings of up to 32 UTF-8 bytes): Ollama's stop sequences
+        (engine/stopseq.py; on the HIP backend matched on the sampled tokens' bytes inside the decode graphs,
+        csrc/stopseq.hip).  The row ends on the token that completes a stop string (``done_reason`` "stop",
+        ``stop_hit`` names the string); ``tokens`` keeps that token, ``text`` is cut where the string starts.  Not
+        together with speculative decoding; the three stop token **ids** are ``options["stop_ids"]``."""
         prompts = list(prompts)
         B = len(prompts)
         if B == 0:
@@ -1094,6 +1187,8 @@ class DecodeEngine:
                or [self.cfg.bos_id] for i, p in enumerate(prompts)]
         nps = [int(num_predict)] * B if isinstance(num_predict, int) else [int(x) for x in num_predict]
         row_opts = [_row_options(o, self.cfg, i, self.seed) for i, o in enumerate(opts)]
+        if self.speculative and any(o["stop_strs"] for o in row_opts):
+            raise ValueError(SPEC_STOP_REFUSAL)
         for i in range(B):
             budget = self.T_max - len(ids[i])
             if budget < 1:
@@ -1103,6 +1198,7 @@ class DecodeEngine:
         lps = None  # per row (logprobs, top_logprobs) or None
         self._last_spec = None
         self._last_json = None
+        self._last_stop = None
         if self.backend == "torch" and self.speculative:
             gen, t_pref, t_dec = self._generate_torch_spec(ids, nps, row_opts, drafts)
             if on_tokens is not None:
@@ -1123,9 +1219,13 @@ class DecodeEngine:
         for i in range(B):
             toks = gen[i]
             js = self._last_json[i] if self._last_json is not None else None
-            reason = "stop" if _stopped(toks, row_opts[i]) or js == "done" else "length"
-            text = self._json_text(toks) if js is not None and self._json_custom else self.tokenizer.decode(toks)
+            hit = self._last_stop[i] if self._last_stop is not None else None
+            reason = "stop" if _stopped(toks, row_opts[i]) or js == "done" or hit is not None else "length"
+            text = self.text_decoder(js is not None, bool(row_opts[i]["stop_strs"])).decode(toks)
+            if hit is not None:
+                text = self.stop_cut(toks, text, hit[0])
             out.append(GenResult(self.cfg.name, ids[i], toks, text, reason, json_state=js,
+                                 stop_hit=row_opts[i]["stop_strs"][hit[1]] if hit is not None else None,
                                  load_duration_ns=load, prompt_eval_duration_ns=t_pref,
                                  eval_duration_ns=int(t_dec * len(toks) / max(1, steps)),
                                  total_duration_ns=total + load))
@@ -1155,6 +1255,8 @@ class DecodeEngine:
         B = len(ids)
         with_lp = want is not None and any(w >= 0 for w in want)
         with_gr = fmt is not None and any(fmt)  # some row in JSON mode: the graphs with the mask and the advance
+        stops = [o["stop_strs"] for o in row_opts]
+        with_st = any(stops)  # some row has stop strings: the graphs with the match after the sampler
         spec = self.speculative > 0  # K + 1 rows per sequence and step: speculative graphs, done polled per chunk
         spec_mode = int(drafts is not None)
         self._forget_slots(range(B))
@@ -1181,6 +1283,10 @@ class DecodeEngine:
             if with_gr:
                 self._gr_begin(slice(0, B), fmt)
                 gq = self._gr_struct()
+            sq = None
+            if with_st:
+                self._st_begin(slice(0, B), stops)
+                sq = self._st_struct()
             self.stream.synchronize()
             t1 = time.perf_counter_ns()
             steps = max(nps)
@@ -1193,7 +1299,9 @@ class DecodeEngine:
                     return
                 if not use_graph:
                     for _ in range(nsteps):
-                        if gq is not None:
+                        if sq is not None:
+                            self._forward(B, r, want_logits=True, want_sample=True, lp=lq, gr=gq, st=sq)
+                        elif gq is not None:
                             self._forward(B, r, want_logits=True, want_sample=True, lp=lq, gr=gq)
                         elif lq is None:  # (the call it always was: wrappers of _forward see the same arguments)
                             self._forward(B, r, want_logits=True, want_sample=True)
@@ -1202,6 +1310,7 @@ class DecodeEngine:
                     return
                 k = self.steps_per_graph
                 graph = (lambda n: self._graph_spec(B, n, spec_mode)) if spec else \
+                    (lambda n: self._graph(B, n, with_lp, with_gr, True)) if with_st else \
                     (lambda n: self._graph(B, n, with_lp, with_gr) if with_gr else self._graph(B, n, with_lp))
                 g = graph(k) if nsteps >= k else None
                 for _ in range(nsteps // k):
@@ -1221,8 +1330,8 @@ class DecodeEngine:
             done_steps = 1
             emitted = [0] * B
             # (speculative: a step commits up to K + 1 tokens, so rows finish in fewer steps than tokens)
-            # (JSON mode: a row ends when its object closes)
-            watch = spec or with_gr or on_tokens is not None or \
+            # (JSON mode: a row ends when its object closes; stop sequences: when a string completes)
+            watch = spec or with_gr or with_st or on_tokens is not None or \
                 any(o["eos_id"] >= 0 or o["stop"] for o in row_opts)
             chunk = self.steps_per_graph * max(1, int(check_every))
 
@@ -1260,6 +1369,8 @@ class DecodeEngine:
                 self._last_spec = [self._spec_stats(i) for i in range(B)]
             if with_gr:
                 self._last_json = self._gr_states(B, fmt)
+            if with_st:
+                self._last_stop = self._st_hits(B, stops)
             t2 = time.perf_counter_ns()
         self.last_ttft_ns = t_first - t0
         return [gen[i, : n_gen[i]].tolist() for i in range(B)], t1 - t0, t2 - t1, lps
@@ -1379,9 +1490,13 @@ class DecodeEngine:
         """Oracle backend with a KV cache (one token of compute per step), sampled on the host; logprobs (``want``
         per row: -1 or the number of alternatives) by ``logprob_host`` of the same logits.  JSON mode (``fmt`` per
         row): the Python automaton masks the logits before the sampler with the device's values and ends the row by
-        the device's rule (engine/jsonmode.py)."""
+        the device's rule (engine/jsonmode.py).  Stop sequences (``row_opts[i]["stop_strs"]``): the Python rule
+        (engine/stopseq.py) over each token's piece, after JSON mode's advance."""
         t0 = time.perf_counter_ns()
         gens = []
+        with_st = any(o["stop_strs"] for o in row_opts)
+        spieces = self._piece_vocab() if with_st else None
+        hits: List[Optional[tuple]] = [None] * len(ids)
         with_gr = fmt is not None and any(fmt)
         pieces = self._json_vocab() if with_gr else None
         jstates: List[Optional[str]] = [None] * len(ids)
@@ -1394,6 +1509,7 @@ class DecodeEngine:
             cache: list = []
             step = torch.tensor([list(p)], device=self.device)
             js = jsonmode.INITIAL if with_gr and fmt[i] else None
+            sstops, ss = stopseq.stop_bytes(o["stop_strs"]), stopseq.INITIAL
             for _ in range(nps[i]):
                 logits = self.ref.forward(step, cache=cache, last_only=True)[0, -1].float().cpu()
                 if js is None:
@@ -1410,11 +1526,17 @@ class DecodeEngine:
                     lps[i][1].append(top)
                 out.append(nxt)
                 step = torch.tensor([[nxt]], device=self.device)
-                if _stopped(out, o) or (js is not None and jsonmode.sid_of(js) == jsonmode.DONE):
+                if sstops:
+                    ss, _ = stopseq.advance(ss, spieces[nxt], sstops)
+                if _stopped(out, o) or (js is not None and jsonmode.sid_of(js) == jsonmode.DONE) or ss[3] >= 0:
                     break
             if js is not None:
                 jstates[i] = {jsonmode.DONE: "done", jsonmode.FAIL: "fail"}.get(jsonmode.sid_of(js), "open")
+            if ss[3] >= 0:
+                hits[i] = (ss[3], ss[4])
             gens.append(out)
+        if with_st:
+            self._last_stop = hits
         if with_gr:
             self._last_json = jstates
         t1 = time.perf_counter_ns()
@@ -1549,6 +1671,7 @@ class ContinuousBatch:
         self.reused: List[int] = []  # per live row: leading prompt tokens its slot already held at admit
         self.want: List[int] = []  # per live row: -1 (no logprobs) or its number of top_logprobs
         self.fmt: List[bool] = []  # per live row: JSON mode
+        self.stops: List[tuple] = []  # per live row: its stop strings (options.stop)
         # prefix-cache bookkeeping per live row (engine.slot_tokens): steps run since admit, the newest polled
         # token (its KV is not written yet), done at the last poll, last position already dropped from the record
         self._steps: List[int] = []
@@ -1558,7 +1681,7 @@ class ContinuousBatch:
 
     def _row_lists(self):
         return (self.row_slot, self.emitted, self.prompt_tokens, self.options, self.reused, self.want, self.fmt,
-                self._steps,
+                self.stops, self._steps,
                 self._pending, self._done, self._trimmed)
 
     def _trim_idled(self) -> None:
@@ -1584,7 +1707,8 @@ class ContinuousBatch:
         """``logprobs`` / ``top_logprobs`` per request (or one value for all) as ``DecodeEngine.generate``: rows that
         ask and rows that do not decode together (``logprobs(row)`` reads a row's).  ``format`` likewise ("json" per
         request, or the option key ``"format"``): a JSON-mode row's automaton state starts fresh here and moves with
-        the row (``json_state(row)`` reads how it stands)."""
+        the row (``json_state(row)`` reads how it stands).  ``options[i]["stop"]``: the request's stop strings, as
+        ``generate``'s (``stop_hit(row)`` reads whether one ended the row)."""
         from .. import ops
 
         eng = self.eng
@@ -1610,6 +1734,9 @@ class ContinuousBatch:
                 raise ValueError(f"prompt of {len(p)} tokens exceeds the context ({eng.T_max})")
             nps.append(max(1, min(int(n), budget)))
             row_opts.append(_row_options(o, eng.cfg, self.n + i, eng.seed))
+        stops = [o["stop_strs"] for o in row_opts]
+        if eng.speculative and any(stops):
+            raise ValueError(SPEC_STOP_REFUSAL)
         if eng.prefix_cache:
             self._trim_idled()
             plan = plan_prefix_reuse(eng.slot_tokens, self.free_slots, self.row_slot, ids, PREFIX_COPY_MIN)
@@ -1651,8 +1778,11 @@ class ContinuousBatch:
                 eng._spec_begin(rows, slots, ids)
             if eng._gr is not None or any(fmt):
                 eng._gr_begin(sl, fmt)
+            if eng._st is not None or any(stops):
+                eng._st_begin(sl, stops)
         self.want += want
         self.fmt += fmt
+        self.stops += stops
         self.n += k
         self.row_slot += slots
         self.emitted += [0] * k
@@ -1679,7 +1809,9 @@ class ContinuousBatch:
         with_lp = any(w >= 0 for w in self.want)  # some live row wants logprobs: the graphs that compute them
         # speculative engines: each step drafts (n-gram lookup), verifies K + 1 rows per live row and commits
         with_gr = any(self.fmt)  # some live row is in JSON mode: the graphs with the mask and the advance
+        with_st = any(self.stops)  # some live row has stop strings: the graphs with the match after the sampler
         graph = (lambda n: eng._graph_spec(self.n, n, 0)) if eng.speculative else \
+            (lambda n: eng._graph(self.n, n, with_lp, with_gr, True)) if with_st else \
             (lambda n: eng._graph(self.n, n, with_lp, with_gr) if with_gr else eng._graph(self.n, n, with_lp))
         with torch.cuda.stream(eng.stream):
             k = eng.steps_per_graph
@@ -1708,6 +1840,14 @@ class ContinuousBatch:
             return None
         with torch.cuda.stream(self.eng.stream):
             return self.eng._gr_states(row + 1, [False] * row + [True])[row]
+
+    def stop_hit(self, row: int) -> Optional[tuple]:
+        """``(hit_start, index)`` of the stop string that ended a live row (the byte offset in its stream where the
+        text is cut, the index in its list); None for a row without stop strings or one that hit none."""
+        if not self.stops[row]:
+            return None
+        with torch.cuda.stream(self.eng.stream):
+            return self.eng._st_hits(row + 1, [()] * row + [self.stops[row]])[row]
 
     def logprobs(self, row: int, lo: int = 0, hi: Optional[int] = None):
         """``(logprobs, top_logprobs)`` of tokens ``lo .. hi - 1`` (default: all polled so far) of a live row that
@@ -1788,6 +1928,9 @@ class ContinuousBatch:
                 if eng._gr is not None:
                     for key in ("gram_on", "gstate"):
                         eng._gr[key][dst] = eng._gr[key][src]
+                if eng._st is not None:
+                    for key in ("stop_on", "sstate", "stop_len", "stop_bytes"):
+                        eng._st[key][dst] = eng._st[key][src]
                 if eng._spec is not None:  # (the records are per slot and stay)
                     for key in ("given", "drafted", "accepted", "n_step", "step_tokens"):
                         eng._spec[key][dst] = eng._spec[key][src]
@@ -1798,6 +1941,8 @@ class ContinuousBatch:
             eng.rows["slot"][n_new: self.n].fill_(-1)  # vacated rows: skipped by the sampler
             if eng._gr is not None:
                 eng._gr["gram_on"][n_new: self.n].zero_()
+            if eng._st is not None:
+                eng._st["stop_on"][n_new: self.n].zero_()
         self.n = n_new
         for lst in self._row_lists():
             del lst[n_new:]

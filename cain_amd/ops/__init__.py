@@ -27,7 +27,8 @@ op                     source                      replaces (Ollama/llama.cpp)
 ``logprob_rows``       csrc/logprob.hip            log-softmax, top-n and token logprobs on device
 ``json_mask``          csrc/grammar.hip            format "json": the JSON grammar as a logit mask on device
 ``json_advance``       csrc/grammar.hip            the rows' automaton states over the sampled tokens
-``spec_draft``         csrc/spec.hip               n-gram / given drafts -> K + 1 expanded rows per sequence
+``stop_advance``       csrc/stopseq.hip            options.stop: stop strings matched over the sampled tokens' bytes
+``spec_draft``         csrc/spec.hip              n-gram / given drafts -> K + 1 expanded rows per sequence
 ``spec_accept``        csrc/spec.hip               commit the longest correct draft prefix (lookup decoding)
 ``spec_model_rows``    csrc/spec.hip               draft-model mode: the draft model's rows per forward, its tokens
 ``spec_model_next``                                into the given drafts, ``dvalid`` per cache slot
@@ -981,6 +982,95 @@ def json_advance(gram_on, gen: torch.Tensor, n_gen, done, gstate, table: dict) -
     return int(lib.cain_json_advance(gen.shape[0], int(table["V"]), _p(gram_on), _p(gen), gen.stride(0), _p(n_gen),
                                      _p(done), _p(gstate), _p(table["piece_off"]), _p(table["piece_bytes"]),
                                      _stream()))
+
+
+# ------------------------------------------------------------ stop sequences (csrc/stopseq.hip, csrc/stop_match.h)
+STOP_STATE_BYTES = 48  # sizeof(StopState): 32 tail bytes, tokens, bytes, hit_start, hit_which
+STOP_MAX = 8
+STOP_LEN_MAX = 32
+
+
+class CainStop(ctypes.Structure):  # csrc/runtime.hip CainStop
+    _fields_ = [("stop_on", vp), ("sstate", vp), ("stop_len", vp), ("stop_bytes", vp), ("piece_off", vp),
+                ("piece_bytes", vp)]
+
+
+def load_stop() -> ctypes.CDLL:
+    """``load()`` with the stop sequences' entry points' signatures set (a library without them: AttributeError)."""
+    lib = load()
+    if not getattr(lib, "_cain_stop_sig", False):
+        lib.cain_stop_advance.argtypes = [ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.cain_plan_forward_st.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp]
+        lib.cain_plan_capture_st.restype = vp
+        lib.cain_plan_capture_st.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, ctypes.POINTER(ci)]
+        if int(lib.cain_stop_state_size()) != STOP_STATE_BYTES or int(lib.cain_stop_size()) != ctypes.sizeof(CainStop) \
+                or int(lib.cain_stop_max()) != STOP_MAX or int(lib.cain_stop_len_max()) != STOP_LEN_MAX:
+            raise NativeOpsUnavailable(f"{LIB_PATH}: stop-sequence records differ from this package's: rebuild "
+                                       f"(python -m cain_amd.build)")
+        lib._cain_stop_sig = True
+    return lib
+
+
+def stop_table_host(rows_of_strings):
+    """``(stop_on [M] int32, stop_len [M, 8] int32, stop_bytes [M, 8, 32] uint8)`` CPU tensors of per-row stop
+    strings (``str`` or ``bytes``; validated by ``engine.stopseq.parse_stop`` upstream: at most 8 of 1 .. 32 bytes)."""
+    import numpy as np
+
+    from ..engine.stopseq import stop_bytes
+
+    M = len(rows_of_strings)
+    on, ln = np.zeros(M, dtype=np.int32), np.zeros((M, STOP_MAX), dtype=np.int32)
+    by = np.zeros((M, STOP_MAX, STOP_LEN_MAX), dtype=np.uint8)
+    for i, row in enumerate(rows_of_strings):
+        bs = stop_bytes(row or ())
+        if len(bs) > STOP_MAX or any(not 1 <= len(b) <= STOP_LEN_MAX for b in bs):
+            raise ValueError(f"row {i}: at most {STOP_MAX} stop strings of 1..{STOP_LEN_MAX} bytes")
+        on[i] = int(bool(bs))
+        for k, b in enumerate(bs):
+            ln[i, k] = len(b)
+            by[i, k, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+    return torch.from_numpy(on), torch.from_numpy(ln), torch.from_numpy(by)
+
+
+def stop_table(rows_of_strings, device):
+    """``stop_table_host`` on ``device``: ``(stop_on, stop_len, stop_bytes)``."""
+    return tuple(t.to(device) for t in stop_table_host(rows_of_strings))
+
+
+def stop_states(states, device) -> torch.Tensor:
+    """``engine.stopseq`` states as the device's ``[M, 48]`` uint8 StopState rows."""
+    import numpy as np
+
+    from ..engine.stopseq import state_bytes
+
+    a = np.frombuffer(b"".join(state_bytes(s) for s in states), dtype=np.uint8).reshape(len(states), STOP_STATE_BYTES)
+    return torch.from_numpy(a.copy()).to(device)
+
+
+def stop_states_host(sstate: torch.Tensor) -> list:
+    """The inverse of ``stop_states``."""
+    from ..engine.stopseq import state_from_bytes
+
+    a = sstate.detach().cpu().contiguous().view(torch.uint8).reshape(-1, STOP_STATE_BYTES).numpy()
+    return [state_from_bytes(r.tobytes()) for r in a]
+
+
+def stop_advance(stop_on, gen: torch.Tensor, n_gen, done, sstate, stop_len, stop_bytes, table: dict) -> int:
+    """AFTER the sampler (and after ``json_advance``): every row with ``stop_on[m] != 0`` that generated a token this
+    step (``n_gen[m]`` is one above the tokens its state has consumed) consumes ``gen[m, n_gen[m] - 1]``; a stop string
+    that ends inside the token's bytes sets ``done[m]`` and the state's ``hit_start`` / ``hit_which``.  Returns the
+    entry's code (non-zero: refused)."""
+    lib = load_stop()
+    _gpu(stop_on, gen, n_gen, done, sstate, stop_len, stop_bytes, table["piece_off"], table["piece_bytes"])
+    assert gen.dtype == torch.int32 and gen.stride(1) == 1 and sstate.is_contiguous()
+    assert stop_len.is_contiguous() and stop_bytes.is_contiguous() and stop_len.dtype == torch.int32
+    M = gen.shape[0]
+    assert sstate.numel() * sstate.element_size() >= M * STOP_STATE_BYTES and stop_len.numel() >= M * STOP_MAX
+    assert stop_bytes.numel() >= M * STOP_MAX * STOP_LEN_MAX and stop_bytes.dtype == torch.uint8
+    assert min(stop_on.numel(), n_gen.numel(), done.numel()) >= M
+    return int(lib.cain_stop_advance(M, int(table["V"]), _p(stop_on), _p(gen), gen.stride(0), _p(n_gen), _p(done),
+                                     _p(sstate), _p(stop_len), _p(stop_bytes), _p(table["piece_off"]),
+                                     _p(table["piece_bytes"]), _stream()))
 
 
 _SAMPLE_WS: dict = {}

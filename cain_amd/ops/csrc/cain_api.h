@@ -75,7 +75,7 @@ CAIN_API float* cain_gemm_cmax_claim(int N);
 // cain_set_cu_budget (runtime.hip) while the work runs on a CU-masked stream (cain_stream_create_cu_limited).
 CAIN_API int cain_cu_budget();
 
-// ---- the rest of a forward (norm.hip, attention.hip, sample.hip, logprob.hip, grammar.hip, spec.hip)
+// ---- the rest of a forward (norm.hip, attention.hip, sample.hip, logprob.hip, grammar.hip, stopseq.hip, spec.hip)
 CAIN_API int cain_embed(const int* tok, const void* E, void* out, int ldo, int M, int d, float scale, hipStream_t st);
 CAIN_API int cain_attention_ex(const void* q, const void* kc, const void* vtc, const int* slot, const int* pos,
                                float* part_o, float* part_ml, unsigned* counters, void* out, int ldo, int M, int H,
@@ -112,6 +112,10 @@ CAIN_API int cain_json_mask(float* logits, int ldl, int V, int M, const int* gra
                             hipStream_t st);
 CAIN_API int cain_json_advance(int M, int V, const int* gram_on, const int* gen, int ldg, int* n_gen, int* done,
                                void* gstate, const int* piece_off, const uint8_t* piece_bytes, hipStream_t st);
+CAIN_API int cain_stop_advance(int M, int V, const int* stop_on, const int* gen, int ldg, const int* n_gen, int* done,
+                               void* sstate, const int32_t* stop_len, const uint8_t* stop_bytes, const int* piece_off,
+                               const uint8_t* piece_bytes, hipStream_t st);
+CAIN_API int cain_stop_state_size();
 CAIN_API int cain_spec_draft(const CainSpec* s, int R, int T_max, const int* tok, const int* pos, const int* slot,
                              const int* n_gen, const int* max_new, const int* done, const int* hist,
                              const void* params, hipStream_t st);

@@ -137,6 +137,17 @@ struct CainGrammar {
   const uint8_t* piece_bytes;
 };
 
+// Stop sequences of a decode forward (stopseq.hip; cain_plan_forward_st / cain_plan_capture_st): the match runs after
+// the sampler, and after JSON mode's advance where that is on too (a token it took back is not consumed).
+struct CainStop {
+  const int* stop_on;          // per row: 0 off, else the row has stop strings
+  void* sstate;                // per row: 48 bytes of StopState (stop_match.h)
+  const int32_t* stop_len;     // [M][8]: bytes of each string, 0 for an unused entry
+  const uint8_t* stop_bytes;   // [M][8][32]
+  const int* piece_off;        // the piece table, as CainGrammar's
+  const uint8_t* piece_bytes;
+};
+
 }  // extern "C"
 
 namespace {
@@ -183,8 +194,9 @@ int max_rows(const CainPlanDesc& d) {
 // O(+residual) -> gate/up(+RMSNorm, act*mul) -> down(+residual); 6 in a layer whose V rows are Q6_K beside Q4 q / k.
 // lq: the caller's logprob buffers (null: none -- the launches are exactly those of a plan without the feature)
 // gr: JSON mode's buffers (null: none, likewise)
+// sq: the stop sequences' buffers (null: none, likewise)
 int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_sample, hipStream_t st,
-            const CainLogprob* lq = nullptr, const CainGrammar* gr = nullptr) {
+            const CainLogprob* lq = nullptr, const CainGrammar* gr = nullptr, const CainStop* sq = nullptr) {
   const CainPlanDesc& d = p.d;
   const int qkv_dim = (d.H + 2 * d.Hkv) * d.hd;
   const int q_dim = d.H * d.hd;
@@ -299,6 +311,9 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
     if (gr)
       CK(cain_json_advance(M, d.V, gr->gram_on, r.gen, r.ldg, r.n_gen, r.done, gr->gstate, gr->piece_off,
                            gr->piece_bytes, st));
+    if (sq)
+      CK(cain_stop_advance(M, d.V, sq->stop_on, r.gen, r.ldg, r.n_gen, r.done, sq->sstate, sq->stop_len,
+                           sq->stop_bytes, sq->piece_off, sq->piece_bytes, st));
   }
   return 0;
 }
@@ -325,6 +340,14 @@ bool gr_args_ok(const CainRows* r, int want_logits, int want_sample, const CainL
   if (!gr) return true;
   if (!want_logits || !want_sample || !r->n_gen || !r->done || !r->gen || r->ldg < 1) return false;
   return gr->gram_on && gr->gstate && gr->piece_off && gr->piece_bytes;
+}
+
+// What the _st entries refuse on top of that: stop sequences on anything but a decode forward (logits, sampler and
+// the rows' sampling state), or with a table or state missing.
+bool st_args_ok(const CainRows* r, int want_logits, int want_sample, const CainStop* sq) {
+  if (!sq) return true;
+  if (!r || !want_logits || !want_sample || !r->n_gen || !r->done || !r->gen || r->ldg < 1) return false;
+  return sq->stop_on && sq->sstate && sq->stop_len && sq->stop_bytes && sq->piece_off && sq->piece_bytes;
 }
 
 bool spec_rows_ok(const Plan& p, int R, const CainRows* r, const CainSpec* s) {
@@ -431,66 +454,53 @@ CAIN_API void cain_w4a8_set_min_rows(int m) { g_w4a8_min_rows = m > 16 ? m : 16;
 
 CAIN_API const char* cain_plan_last_failure() { return g_fail; }
 
-CAIN_API int cain_plan_forward(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
-                               hipStream_t st) {
+// The decode forward with stop sequences (CainStop), under JSON mode when `gr` is given and with token
+// log-probabilities when `lq` is: `gr` and `sq` need want_logits and want_sample (refused before any launch
+// otherwise); with all three null it runs what cain_plan_forward runs.
+CAIN_API int cain_plan_forward_st(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
+                                  const CainLogprob* lq, const CainGrammar* gr, const CainStop* sq, hipStream_t st) {
   auto* p = static_cast<Plan*>(plan);
   g_fail[0] = 0;
-  if (M < 1 || M > max_rows(p->d)) return -1;
-  return forward(*p, M, *rows, want_logits, want_sample, st);
+  if (M < 1 || M > max_rows(p->d) || !gr_args_ok(rows, want_logits, want_sample, lq, gr) ||
+      !st_args_ok(rows, want_logits, want_sample, sq))
+    return -1;
+  return forward(*p, M, *rows, want_logits, want_sample, st, lq, gr, sq);
+}
+
+CAIN_API int cain_plan_forward(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
+                               hipStream_t st) {
+  return cain_plan_forward_st(plan, M, rows, want_logits, want_sample, nullptr, nullptr, nullptr, st);
 }
 
 // The same forward with token log-probabilities (CainLogprob): needs want_logits; a null `lq` is cain_plan_forward.
 CAIN_API int cain_plan_forward_lp(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
                                   const CainLogprob* lq, hipStream_t st) {
-  auto* p = static_cast<Plan*>(plan);
-  g_fail[0] = 0;
-  if (M < 1 || M > max_rows(p->d)) return -1;
-  return forward(*p, M, *rows, want_logits, want_sample, st, lq);
+  return cain_plan_forward_st(plan, M, rows, want_logits, want_sample, lq, nullptr, nullptr, st);
 }
 
-// The decode forward under JSON mode (CainGrammar), with token log-probabilities when `lq` is given too: needs
-// want_logits and want_sample (refused before any launch otherwise); a null `gr` runs what cain_plan_forward_lp runs.
+// The decode forward under JSON mode (CainGrammar): cain_plan_forward_st without stop sequences.
 CAIN_API int cain_plan_forward_gr(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
                                   const CainLogprob* lq, const CainGrammar* gr, hipStream_t st) {
-  auto* p = static_cast<Plan*>(plan);
-  g_fail[0] = 0;
-  if (M < 1 || M > max_rows(p->d) || !gr_args_ok(rows, want_logits, want_sample, lq, gr)) return -1;
-  return forward(*p, M, *rows, want_logits, want_sample, st, lq, gr);
+  return cain_plan_forward_st(plan, M, rows, want_logits, want_sample, lq, gr, nullptr, st);
 }
 
 // Record `steps` decode steps over M rows into a graph; returns the executable graph (or null).  Each step with its
-// token log-probabilities when `lq` is given and under JSON mode when `gr` is (both null: the graph of
-// cain_plan_capture, launch for launch).
-CAIN_API void* cain_plan_capture_gr(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
-                                    const CainGrammar* gr, hipStream_t st, int* err) {
+// token log-probabilities when `lq` is given, under JSON mode when `gr` is and with stop sequences when `sq` is (all
+// null: the graph of cain_plan_capture, launch for launch).
+CAIN_API void* cain_plan_capture_st(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
+                                    const CainGrammar* gr, const CainStop* sq, hipStream_t st, int* err) {
   auto* p = static_cast<Plan*>(plan);
   *err = 0;
-  if (M < 1 || M > max_rows(p->d) || steps < 1 || !gr_args_ok(rows, 1, 1, lq, gr)) {
+  if (M < 1 || M > max_rows(p->d) || steps < 1 || !gr_args_ok(rows, 1, 1, lq, gr) || !st_args_ok(rows, 1, 1, sq)) {
     *err = -1;
     return nullptr;
   }
-  hipGraph_t g = nullptr;
-  hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-  if (e != hipSuccess) {
-    *err = int(e);
-    return nullptr;
-  }
-  int fe = 0;
-  for (int s = 0; s < steps && fe == 0; ++s) fe = forward(*p, M, *rows, 1, 1, st, lq, gr);
-  e = hipStreamEndCapture(st, &g);
-  if (fe != 0 || e != hipSuccess) {
-    *err = fe ? fe : int(e);
-    if (g) (void)hipGraphDestroy(g);
-    return nullptr;
-  }
-  hipGraphExec_t ex = nullptr;
-  e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (e != hipSuccess) {
-    *err = int(e);
-    return nullptr;
-  }
-  return ex;
+  return capture_steps(st, steps, err, [&] { return forward(*p, M, *rows, 1, 1, st, lq, gr, sq); });
+}
+
+CAIN_API void* cain_plan_capture_gr(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
+                                    const CainGrammar* gr, hipStream_t st, int* err) {
+  return cain_plan_capture_st(plan, M, rows, steps, lq, gr, nullptr, st, err);
 }
 
 CAIN_API void* cain_plan_capture_lp(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
@@ -607,6 +617,7 @@ CAIN_API int cain_stream_destroy(void* st) { return hipStreamDestroy(static_cast
 CAIN_API int cain_rows_size() { return int(sizeof(CainRows)); }
 CAIN_API int cain_logprob_size() { return int(sizeof(CainLogprob)); }
 CAIN_API int cain_grammar_size() { return int(sizeof(CainGrammar)); }
+CAIN_API int cain_stop_size() { return int(sizeof(CainStop)); }
 CAIN_API int cain_plan_desc_size() { return int(sizeof(CainPlanDesc)); }
 CAIN_API int cain_layer_size() { return int(sizeof(CainLayer)); }
 

@@ -46,6 +46,15 @@ graphs, csrc/grammar.hip).  The row ends on the brace that closes the object (``
 text, exactly as before.  A JSON schema object or any other value is a 400; so is ``format`` on a ``--speculative``
 server, and on a model whose vocabulary cannot spell JSON (the synthetic tokenizer of the random-init tags).
 
+Stop sequences: ``options.stop`` (a string or a list of up to 8 strings of up to 32 UTF-8 bytes) on ``/api/generate``
+and ``/api/chat`` ends the generation on the token that completes one of the strings (engine/stopseq.py; on the HIP
+backend matched inside the decode graphs, csrc/stopseq.hip): ``done_reason: "stop"``, the response without the string
+and what followed it inside that token, ``eval_count`` with that token.  While such a row streams, the server holds
+back the longest end of its output that may yet begin a stop string (``StopStreamer``), so the streamed pieces
+concatenate to exactly the non-streamed response.  Anything else in ``stop`` is a 400; so is ``stop`` on a
+``--speculative`` server.  Special tokens cannot be matched as text (their pieces are empty): they are what the
+template's turn-end ids and the engine's ``stop_ids`` are for.
+
 Tracing: started with ``--trace-dir DIR``, the engine backend records every decode batch
 with ``torch.profiler`` (host ops + GPU kernels) and writes a Chrome trace to DIR; the response JSON
 names it in ``cain_trace`` so the client can file it with its run (the study moves it into run_dir).
@@ -115,6 +124,43 @@ def logprob_entries(tok, ids, lps, tops) -> List[Dict[str, Any]]:
     return [dict(one(i, lp), top_logprobs=[one(a, v) for a, v in top]) for i, lp, top in zip(ids, lps, tops)]
 
 
+class StopStreamer:
+    """The streamed text of a row with stop strings, in ``StreamDecoder``'s place.  After every ``push`` the text sent
+    so far is a prefix of whatever the row's final text can still be: the host runs the row's stop rule over the new
+    tokens' pieces (engine/stopseq.py) and sends the decoded text cut before the longest end of the stream that is a
+    proper prefix of a stop string -- or, once a string completed, cut where the engine cuts it.  ``finish(text)``
+    sends what remains of the final text.  (Each push decodes the whole row: stop rows only.)"""
+
+    def __init__(self, eng, stops, decoder):
+        from ..engine import stopseq
+
+        self.rule, self.pieces, self.dec = stopseq, eng._piece_vocab(), decoder
+        self.stops = stopseq.stop_bytes(stops)
+        self.ids: List[int] = []
+        self.raw = bytearray()
+        self.state = stopseq.INITIAL
+        self.sent = ""
+
+    def push(self, ids) -> str:
+        for t in ids:
+            piece = self.pieces[t] if 0 <= int(t) < len(self.pieces) else b""
+            self.ids.append(int(t))
+            self.raw += piece
+            if self.state[3] < 0:
+                self.state, _ = self.rule.advance(self.state, piece, self.stops)
+        raw = bytes(self.raw)
+        cut = self.state[3] if self.state[3] >= 0 else len(raw) - self.rule.held_back(raw, self.stops)
+        text = self.rule.cut_text(self.dec.decode(self.ids), raw, cut)
+        if text.endswith("\ufffd") or len(text) <= len(self.sent) or not text.startswith(self.sent):
+            return ""  # (a character still split over tokens, or nothing new)
+        piece, self.sent = text[len(self.sent):], text
+        return piece
+
+    def finish(self, text: str) -> str:
+        piece, self.sent = text[len(self.sent):], text
+        return piece
+
+
 class Backend:
     """Interface: decode a batch of jobs for one model."""
 
@@ -142,6 +188,10 @@ class Backend:
     def check_format(self, model: str, fmt: str) -> None:
         """Raise ValueError when this backend cannot serve ``format: fmt`` for ``model`` (default: the field is
         accepted and ignored, as a backend without a model does)."""
+
+    def check_stop(self, model: str, stops) -> None:
+        """Raise ValueError when this backend cannot serve ``options.stop`` for ``model`` (default: the option is
+        accepted; a backend without a model ignores it, as it ignores the sampling options)."""
 
     def vocab_size(self, model: str) -> Optional[int]:
         """Token ids a request's ``context`` may hold are below this (None: not checked)."""
@@ -309,11 +359,22 @@ class EngineBackend(Backend):
             return
         self.engine(model)._json_vocab()
 
+    def check_stop(self, model: str, stops) -> None:
+        if stops and self.speculative:
+            raise ValueError("stop strings cannot be combined with speculative decoding (--speculative)")
+
+    @staticmethod
+    def _stream_decoder(eng, j: Job):
+        """What turns a streamed job's new token ids into the text pieces to send."""
+        stops = j.options.get("stop") if j.options else None
+        dec = eng.text_decoder(bool(j.format), bool(stops))
+        return StopStreamer(eng, stops, dec) if stops else StreamDecoder(dec)
+
     def run(self, model: str, jobs: List[Job]) -> None:
         eng = self.engine(model)
         tok = eng.tokenizer
         streams = [j.stream for j in jobs]
-        decs = [StreamDecoder(eng.text_decoder(bool(j.format))) for j in jobs]
+        decs = [self._stream_decoder(eng, j) if j.stream is not None else None for j in jobs]
 
         def on_tokens(new_per_row: List[List[int]], lps=None) -> None:
             for r, (j, d, ids) in enumerate(zip(jobs, decs, new_per_row)):
@@ -344,7 +405,8 @@ class EngineBackend(Backend):
         ttft = getattr(eng, "last_ttft_ns", 0)
         for j, d, r in zip(jobs, decs, res):
             if j.stream is not None:
-                tail = d.flush()  # text held back at a length cutoff inside a character
+                # text held back at a length cutoff inside a character; a stop row: what remains of its final text
+                tail = d.finish(r.text) if isinstance(d, StopStreamer) else d.flush()
                 if tail:
                     j.stream(tail)
             if j.logprobs and j.stream is None:
@@ -419,7 +481,7 @@ class EngineBackend(Backend):
             t_first = time.perf_counter_ns()
             for r, j in zip(rows, ok):
                 live[r] = {"job": j, "t0": t0, "t_pre": t_pre, "t_first": t_first,
-                           "dec": StreamDecoder(eng.text_decoder(bool(j.format)))}
+                           "dec": EngineBackend._stream_decoder(eng, j) if j.stream is not None else None}
         cb.step()
         new, fin = cb.poll()
         now = time.perf_counter_ns()
@@ -437,14 +499,18 @@ class EngineBackend(Backend):
         for r in done_rows:
             st, j = live[r], live[r]["job"]
             toks = cb.tokens(r)
+            js = cb.json_state(r)  # JSON mode: the row ended on the brace that closes its object
+            hit = cb.stop_hit(r)  # stop sequences: the row ended on the token that completed one of its strings
+            text = eng.text_decoder(js is not None, bool(cb.stops[r])).decode(toks)
+            if hit is not None:
+                text = eng.stop_cut(toks, text, hit[0])
             if j.stream is not None:
-                tail = st["dec"].flush()
+                tail = st["dec"].finish(text) if isinstance(st["dec"], StopStreamer) else st["dec"].flush()
                 if tail:
                     j.stream(tail)
-            js = cb.json_state(r)  # JSON mode: the row ended on the brace that closes its object
-            reason = "stop" if _stopped(toks, cb.options[r]) or js == "done" else "length"
-            j.result = GenResult(model, list(cb.prompt_tokens[r]), toks,
-                                 eng.text_decoder(js is not None).decode(toks), reason, json_state=js,
+            reason = "stop" if _stopped(toks, cb.options[r]) or js == "done" or hit is not None else "length"
+            j.result = GenResult(model, list(cb.prompt_tokens[r]), toks, text, reason, json_state=js,
+                                 stop_hit=cb.stops[r][hit[1]] if hit is not None else None,
                                  load_duration_ns=0, prompt_eval_duration_ns=int(st["t_pre"] - st["t0"]),
                                  eval_duration_ns=int(now - st["t_pre"]),
                                  total_duration_ns=int(now - j.t_submit * 1e9), prompt_cached=int(cb.reused[r]),
@@ -719,6 +785,15 @@ class OllamaHandler(BaseHTTPRequestHandler):
                 return self._send_json(404, {"error": str(exc).strip("'\"")})
             except ValueError as exc:
                 return self._send_json(400, {"error": str(exc)})
+        # Ollama's options.stop: a string or a list of strings (engine/stopseq.py has the limits)
+        if opts.get("stop") is not None:
+            from ..engine.stopseq import parse_stop
+
+            try:
+                opts["stop"] = list(parse_stop(opts["stop"]))
+                self.scheduler.backend.check_stop(model, opts["stop"])
+            except ValueError as exc:
+                return self._send_json(400, {"error": str(exc)})
         n = opts.get("num_predict")
         # the length policy reads the user's words ("In N words ..."), not the template around them
         num_predict = int(n) if n is not None and int(n) > 0 else default_num_predict(text)
@@ -906,12 +981,23 @@ def generate_main(argv: Optional[List[str]] = None) -> None:
                     help="with --speculative: the model that proposes the drafts")
     ap.add_argument("--format", choices=["json"], default=None,
                     help="json: constrain the output to a JSON object (Ollama's format: \"json\")")
+    ap.add_argument("--stop", action="append", metavar="STR",
+                    help="end the generation where STR appears in the output (repeatable, up to 8; Ollama's "
+                         "options.stop)")
     ns = ap.parse_args(argv)
     if ns.checkpoint:
         register_checkpoints([f"{ns.model}={ns.checkpoint}"])
     be = EngineBackend([ns.model], device=ns.device, max_batch=1, weight_dtype=ns.weights, kv_dtype=ns.kv,
                        speculative=ns.speculative, draft_model=_draft_model_arg(ns.draft_model, ns.speculative))
     opts = {k: v for k, v in (("temperature", ns.temperature), ("seed", ns.seed)) if v is not None}
+    if ns.stop:
+        from ..engine.stopseq import parse_stop
+
+        try:
+            opts["stop"] = list(parse_stop(ns.stop))
+            be.check_stop(ns.model, opts["stop"])
+        except ValueError as exc:
+            raise SystemExit(f"--stop: {exc}")
     job = Job(ns.model, ns.prompt, ns.num_predict or default_num_predict(ns.prompt), opts, format=ns.format)
     if ns.format:
         try:
