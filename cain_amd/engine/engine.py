@@ -27,6 +27,7 @@ first decode step's input, so no separate prefill LM-head path exists.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -41,6 +42,7 @@ import torch
 from ..models.config import ModelConfig, get_config, rope_inv_freq
 from ..models.hf import checkpoint_for, load_hf_weights, load_pretrained, load_tokenizer
 from ..models.tokenizer import get_tokenizer
+from .. import ops
 from . import jsonmode, stopseq
 from .speculative import K_MAX, SeqState, draft_model_given, draft_model_rows, draft_token, dvalid_after
 from .speculative import draft as spec_draft_host
@@ -153,36 +155,10 @@ def _stopped(toks: List[int], o: Dict) -> bool:
     return bool(toks) and ((o["eos_id"] >= 0 and toks[-1] == o["eos_id"]) or toks[-1] in o.get("stop", ()))
 
 
-# ============================================================== ctypes structs
-LAYER_FIELDS = ("wqkv", "bqkv", "wo", "wgu", "wdown", "sqkv", "so", "sgu", "sdown", "wqkv8", "wo8", "wgu8", "wdown8")
-LAYER_FORMATS = ("fqkv", "fo", "fgu", "fdown")  # per-matrix format ids of a GGUF plan, then the split V
+# ============================================================== the plan's formats (records: ops CainPlanDesc ...)
 WFMT = {"bf16": 0, "fp8": 1, "fp4": 2, "q4_0": 3, "q4_k": 4, "q4_k_m": 4}  # runtime.hip WFMT_* (q4_k_m: Q4_K + MFMT)
 MFMT = {0: 3, 1: 4, 2: 5}  # models/q4.py format id -> runtime.hip WFMT_Q4_0 / WFMT_Q4_K / MFMT_Q6_K
 Q4_DTYPES = ("q4_0", "q4_k", "q4_k_m")
-
-
-class _CainLayer(ctypes.Structure):
-    _fields_ = ([(n, ctypes.c_void_p) for n in LAYER_FIELDS] + [(n, ctypes.c_int) for n in LAYER_FORMATS]
-                + [("wv", ctypes.c_void_p), ("sv", ctypes.c_void_p)])
-
-
-class _CainPlanDesc(ctypes.Structure):
-    _fields_ = ([(n, ctypes.c_int) for n in ("n_layers", "d", "H", "Hkv", "hd", "ffn", "V", "act_kind", "T_max",
-                                            "Mpad", "nsplit", "waves")]
-                + [(n, ctypes.c_float) for n in ("eps", "embed_scale", "attn_scale")]
-                + [(n, ctypes.c_void_p) for n in ("embed", "lm_head", "layers", "kcache", "vtcache")]
-                + [("kv_layer_elems", ctypes.c_longlong)]
-                + [(n, ctypes.c_void_p) for n in ("cos_t", "sin_t", "x", "q", "attn", "act", "logits",
-                                                 "part_o", "part_ml", "counters", "gemm_ws")]
-                + [("gemm_ws_bytes", ctypes.c_longlong), ("wfmt", ctypes.c_int), ("lm_head_scale", ctypes.c_void_p)]
-                + [("kv8", ctypes.c_int), ("lm_head8", ctypes.c_void_p), ("x8", ctypes.c_void_p),
-                   ("xs", ctypes.c_void_p), ("x8_ld", ctypes.c_int), ("q4_gain", ctypes.c_int),
-                   ("flm_head", ctypes.c_int)])
-
-
-class _CainRows(ctypes.Structure):
-    _fields_ = ([(n, ctypes.c_void_p) for n in ("tok", "pos", "slot", "n_gen", "max_new", "done", "hist", "gen")]
-                + [("ldg", ctypes.c_int), ("sample_params", ctypes.c_void_p)])
 
 
 def _want_format(format, opts: Sequence[Optional[Dict]], B: int) -> List[bool]:
@@ -198,12 +174,6 @@ def _want_format(format, opts: Sequence[Optional[Dict]], B: int) -> List[bool]:
             raise ValueError(f'format must be "json" or absent, got {f!r}')
         out.append(f == "json")
     return out
-
-
-class _CainLogprob(ctypes.Structure):  # runtime.hip CainLogprob
-    _fields_ = [("topn", ctypes.c_void_p), ("nmax", ctypes.c_int), ("lp", ctypes.c_void_p),
-                ("top_id", ctypes.c_void_p), ("top_lp", ctypes.c_void_p), ("keep", ctypes.c_void_p),
-                ("target", ctypes.c_void_p)]
 
 
 TOP_LOGPROBS_MAX = 20  # Ollama's limit; the entries per token of the device buffers (csrc/logprob.hip LP_TOP)
@@ -258,11 +228,6 @@ def _want_logprobs(logprobs, top_logprobs, B: int) -> List[int]:
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
-
-
-def _set_cu_budget(lib, n: int) -> None:
-    if n or hasattr(lib, "cain_set_cu_budget"):  # (older A/B builds have no CU budget; they never run cu_limit)
-        lib.cain_set_cu_budget(n)
 
 
 def attention_splits(M: int, Hkv: int, T_max: int) -> int:
@@ -587,8 +552,6 @@ class DecodeEngine:
 
     # ---------------------------------------------------------------- hip setup
     def _init_hip(self) -> None:
-        from .. import ops
-
         self.lib = ops.load()
         cfg, dev = self.cfg, self.device
         if self.device.type != "cuda":
@@ -624,19 +587,18 @@ class DecodeEngine:
                          n_gen=z(R, dt=i32), max_new=z(R, dt=i32), done=z(R, dt=i32), hist=z(R * 64, dt=i32))
         self.gen = z(R, self.T_max, dt=i32)
         self.prefill_rows = dict(tok=z(R, dt=i32), pos=z(R, dt=i32), slot=torch.full((R,), -1, device=dev, dtype=i32))
-        from .. import ops as _ops
-        self.sample_params = _ops.sample_params_tensor(
+        self.sample_params = ops.sample_params_tensor(
             [dict(temperature=0.0, top_p=1.0, repeat_penalty=1.0, top_k=1, repeat_last_n=0, eos_id=-1, seed=0)] * R,
             dev)
         if self.weight_dtype in Q4_DTYPES:
             self._check_gguf_shapes(packed)
-        self._layers = (_CainLayer * L)()
+        self._layers = (ops.CainLayer * L)()
         for i, lp in enumerate(packed["layers"]):
-            self._layers[i] = _CainLayer(*(_ptr(lp.get(k)) for k in LAYER_FIELDS),
-                                         *(MFMT[lp[k]] if k in lp else 0 for k in LAYER_FORMATS),
-                                         _ptr(lp.get("wv")), _ptr(lp.get("sv")))
+            self._layers[i] = ops.CainLayer(*(_ptr(lp.get(k)) for k in ops.LAYER_FIELDS),
+                                            *(MFMT[lp[k]] if k in lp else 0 for k in ops.LAYER_FORMATS),
+                                            _ptr(lp.get("wv")), _ptr(lp.get("sv")))
         self._packed = packed
-        d = _CainPlanDesc()
+        d = ops.CainPlanDesc()
         d.n_layers, d.d, d.H, d.Hkv, d.hd = L, cfg.d_model, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
         d.ffn, d.V, d.act_kind, d.T_max, d.Mpad = cfg.ffn, cfg.vocab, 1 if cfg.act == "gelu_tanh" else 0, T, R
         d.nsplit, d.waves = 1, 0
@@ -713,7 +675,6 @@ class DecodeEngine:
         widest forward: the default rule, or ``CAIN_WGEMM_PLANS="N:K:BM:KS[:VARIANT],..."`` (explicit per-shape
         plans for in-graph A/B runs; measured in the graph-replayed decode, never by isolated timings -- an
         isolated autotune's winners did not move the headline, profiles/wgemm_r2.md)."""
-        from .. import ops
         for spec in filter(None, os.environ.get("CAIN_WGEMM_PLANS", "").split(",")):
             f = [int(x) for x in spec.split(":")]
             ops.set_wide_gemm_plan(f[0], f[1], f[2], f[3], f[4] if len(f) > 4 else -1)
@@ -736,8 +697,8 @@ class DecodeEngine:
             self._plans[ns] = self.lib.cain_plan_create(ctypes.byref(self._desc))
         return self._plans[ns]
 
-    def _rows_struct(self, rows: Dict[str, torch.Tensor], with_sampling: bool) -> _CainRows:
-        r = _CainRows()
+    def _rows_struct(self, rows: Dict[str, torch.Tensor], with_sampling: bool) -> ops.CainRows:
+        r = ops.CainRows()
         r.tok, r.pos, r.slot = _ptr(rows["tok"]), _ptr(rows["pos"]), _ptr(rows["slot"])
         if with_sampling:
             r.n_gen, r.max_new, r.done = _ptr(rows["n_gen"]), _ptr(rows["max_new"]), _ptr(rows["done"])
@@ -750,8 +711,6 @@ class DecodeEngine:
         ``topn`` (-1: not wanted; ``s_topn``: of ``score``'s rows), rings indexed like ``gen`` (``lp [R, T]``, ``top_id / top_lp [R, T, 20]``), the
         scratch between the two launches of a decode step, and the per-row targets and results of ``score``."""
         if self._lp is None:
-            from .. import ops
-
             dev, R, T, K = self.device, self.gen.shape[0], self.T_max, TOP_LOGPROBS_MAX
             z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)  # noqa: E731
             self._lp = dict(topn=torch.full((R,), -1, device=dev, dtype=torch.int32), lp=z(R, T),
@@ -761,9 +720,9 @@ class DecodeEngine:
                             s_top_lp=z(R, K))
         return self._lp
 
-    def _lp_struct(self, decode: bool, nmax: int = TOP_LOGPROBS_MAX) -> _CainLogprob:
+    def _lp_struct(self, decode: bool, nmax: int = TOP_LOGPROBS_MAX) -> ops.CainLogprob:
         b = self._lp_bufs()
-        q = _CainLogprob()
+        q = ops.CainLogprob()
         q.topn, q.nmax = _ptr(b["topn" if decode else "s_topn"]), int(nmax)
         if decode:
             assert b["lp"].stride(0) == self.gen.stride(0)
@@ -827,8 +786,6 @@ class DecodeEngine:
         """Device buffers of the stop sequences (csrc/stopseq.hip): per decode row the flag, the match state and the
         strings, and the vocabulary's piece table (JSON mode's tensors when it has made them: the same pieces)."""
         if self._st is None:
-            from .. import ops
-
             R, dev = self.gen.shape[0], self.device
             pieces = self._piece_vocab()
             table = {k: self._gr[k] for k in ("V", "piece_off", "piece_bytes")} if self._gr is not None \
@@ -839,8 +796,6 @@ class DecodeEngine:
         return self._st
 
     def _st_struct(self):
-        from .. import ops
-
         b, q = self._st_bufs(), ops.CainStop()
         q.stop_on, q.sstate, q.stop_len, q.stop_bytes = (_ptr(b["stop_on"]), _ptr(b["sstate"]), _ptr(b["stop_len"]),
                                                          _ptr(b["stop_bytes"]))
@@ -849,8 +804,6 @@ class DecodeEngine:
 
     def _st_begin(self, rows: slice, stops: Sequence[Sequence[str]]) -> None:
         """Decode rows ``rows`` start requests: their stop strings, every state at the start of a stream."""
-        from .. import ops
-
         b = self._st_bufs()
         on, ln, by = ops.stop_table_host(stops)
         b["stop_on"][rows].copy_(on)
@@ -860,8 +813,6 @@ class DecodeEngine:
 
     def _st_hits(self, n: int, stops: Sequence[Sequence[str]]) -> List[Optional[tuple]]:
         """Per decode row ``0 .. n - 1``: ``(hit_start, index)`` of the stop string that ended it, or None."""
-        from .. import ops
-
         st = ops.stop_states_host(self._st_bufs()["sstate"][:n])
         return [(s[3], s[4]) if stops[i] and s[3] >= 0 else None for i, s in enumerate(st)]
 
@@ -869,8 +820,6 @@ class DecodeEngine:
         """Device buffers of JSON mode (csrc/grammar.hip): per decode row the mode flag and the automaton state, and
         the vocabulary's piece table."""
         if self._gr is None:
-            from .. import ops
-
             R = self.gen.shape[0]
             self._gr = dict(ops.json_table(self._json_vocab(), self.device),
                             gram_on=torch.zeros(R, device=self.device, dtype=torch.int32),
@@ -878,8 +827,6 @@ class DecodeEngine:
         return self._gr
 
     def _gr_struct(self):
-        from .. import ops
-
         b, g = self._gr_bufs(), ops.CainGrammar()
         g.gram_on, g.gstate = _ptr(b["gram_on"]), _ptr(b["gstate"])
         g.piece_off, g.piece_bytes = _ptr(b["piece_off"]), _ptr(b["piece_bytes"])
@@ -892,44 +839,59 @@ class DecodeEngine:
         b["gstate"][rows].zero_()  # jsonmode.INITIAL
 
     def _gr_states(self, n: int, fmt: Sequence[bool]) -> List[Optional[str]]:
-        from .. import ops
-
         names = {jsonmode.DONE: "done", jsonmode.FAIL: "fail"}
         st = ops.json_states_host(self._gr_bufs()["gstate"][:n])
         return [names.get(jsonmode.sid_of(s), "open") if f else None for s, f in zip(st, fmt)]
 
-    def _forward(self, M: int, rows, want_logits: bool, want_sample: bool, lp: Optional[_CainLogprob] = None,
-                 gr=None, st=None) -> None:
-        rs = self._rows_struct(rows, want_sample)
-        plan = self._plan(M)
-        _set_cu_budget(self.lib, self.cu_limit)  # launch sizing for this engine's stream (0: whole device)
+    @contextlib.contextmanager
+    def _cu_budget(self):
+        """Around every native call that launches or captures for this engine's stream: the launch sizing of a
+        CU-limited engine (0: the whole device)."""
+        self.lib.cain_set_cu_budget(self.cu_limit)
         try:
-            if st is not None:
-                from .. import ops
-
-                rc = ops.load_stop().cain_plan_forward_st(
-                    ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits), int(want_sample),
-                    ctypes.byref(lp) if lp is not None else None, ctypes.byref(gr) if gr is not None else None,
-                    ctypes.byref(st), ctypes.c_void_p(self.stream.cuda_stream))
-            elif gr is not None:
-                from .. import ops
-
-                rc = ops.load_grammar().cain_plan_forward_gr(
-                    ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits), int(want_sample),
-                    ctypes.byref(lp) if lp is not None else None, ctypes.byref(gr),
-                    ctypes.c_void_p(self.stream.cuda_stream))
-            elif lp is not None:
-                rc = self.lib.cain_plan_forward_lp(ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits),
-                                                   int(want_sample), ctypes.byref(lp),
-                                                   ctypes.c_void_p(self.stream.cuda_stream))
-            else:
-                rc = self.lib.cain_plan_forward(ctypes.c_void_p(plan), M, ctypes.byref(rs), int(want_logits),
-                                                int(want_sample), ctypes.c_void_p(self.stream.cuda_stream))
+            yield
         finally:
-            _set_cu_budget(self.lib, 0)
-        if rc != 0:
-            where = self.lib.cain_plan_last_failure()
-            raise RuntimeError(f"cain_plan_forward failed rc={rc}" + (f" at {where.decode()}" if where else ""))
+            self.lib.cain_set_cu_budget(0)
+
+    def _stream_h(self) -> ctypes.c_void_p:
+        return ctypes.c_void_p(self.stream.cuda_stream)
+
+    def _step(self, M: int, rows, want_logits: bool, want_sample: bool, lp: Optional[ops.CainLogprob] = None,
+              gr: Optional[ops.CainGrammar] = None, st: Optional[ops.CainStop] = None,
+              spec_mode: Optional[int] = None) -> ops.CainStep:
+        """The call record of one step (csrc/cain_api.h CainStep): a forward over ``M`` rows with the given feature
+        records, or -- ``spec_mode`` given (0: n-gram drafts, 1: the given drafts) -- a speculative step over ``M``
+        sequences, whose drafts the draft model proposes where the engine has one.  The record points into the
+        others, so it holds them (``keep``) for as long as it lives."""
+        spec = spec_mode is not None
+        s = ops.CainStep(plan=self._plan(M * (self.speculative + 1) if spec else M), M=M,
+                         want_logits=int(want_logits), want_sample=int(want_sample))
+        sp = sd = None
+        if spec and self.draft is not None:
+            s.draft2, s.draft1 = self.draft._plan(2 * M), self.draft._plan(M)
+            sp, sd = ops.spec_struct(self._spec_bufs(), 1), ops.spec_draft_struct(self._spec_draft_bufs())
+        elif spec:
+            sp = ops.spec_struct(self._spec_bufs(), spec_mode)
+        s.keep = (self._rows_struct(rows, bool(want_sample)), lp, gr, st, sp, sd)
+        for name, rec in zip(("rows", "lp", "gr", "st", "spec", "spec_draft"), s.keep):
+            if rec is not None:
+                setattr(s, name, ctypes.pointer(rec))
+        return s
+
+    def _forward(self, M: int, rows, want_logits: bool, want_sample: bool, lp: Optional[ops.CainLogprob] = None,
+                 gr=None, st=None) -> None:
+        step = self._step(M, rows, want_logits, want_sample, lp, gr, st)
+        with self._cu_budget():
+            ops.step_run(step, self._stream_h())
+
+    def _captured(self, key: tuple, steps: int, make_step) -> int:
+        """The cached graph ``key``: ``steps`` steps of ``make_step()``'s record, captured at first use."""
+        g = self._graphs.get(key)
+        if g is None:
+            step = make_step()
+            with self._cu_budget():
+                g = self._graphs[key] = ops.step_capture(step, steps, self._stream_h())
+        return g
 
     def _graph(self, M: int, steps: int, lp: bool = False, gr: bool = False, st: bool = False) -> int:
         """``lp``: the steps also compute token log-probabilities (for the rows whose ``topn`` says so when the graph
@@ -937,50 +899,28 @@ class DecodeEngine:
         ``gr``: the steps run JSON mode's mask and advance (for the rows whose ``gram_on`` says so), likewise.
         ``st``: the steps match the stop sequences (for the rows whose ``stop_on`` says so), likewise."""
         key = (M, steps) + (("lp",) if lp else ()) + (("gr",) if gr else ()) + (("st",) if st else ())
-        g = self._graphs.get(key)
-        if g is None:
-            rs = self._rows_struct(self.rows, True)
-            err = ctypes.c_int(0)
-            plan = self._plan(M)
-            _set_cu_budget(self.lib, self.cu_limit)
-            try:
-                if st:
-                    from .. import ops
+        return self._captured(key, steps, lambda: self._step(
+            M, self.rows, True, True, self._lp_struct(True) if lp else None, self._gr_struct() if gr else None,
+            self._st_struct() if st else None))
 
-                    q, gs, ss = (self._lp_struct(True) if lp else None), (self._gr_struct() if gr else None), \
-                        self._st_struct()
-                    g = ops.load_stop().cain_plan_capture_st(
-                        ctypes.c_void_p(plan), M, ctypes.byref(rs), steps, ctypes.byref(q) if lp else None,
-                        ctypes.byref(gs) if gr else None, ctypes.byref(ss), ctypes.c_void_p(self.stream.cuda_stream),
-                        ctypes.byref(err))
-                elif gr:
-                    from .. import ops
-
-                    q, gs = (self._lp_struct(True) if lp else None), self._gr_struct()
-                    g = ops.load_grammar().cain_plan_capture_gr(
-                        ctypes.c_void_p(plan), M, ctypes.byref(rs), steps, ctypes.byref(q) if lp else None,
-                        ctypes.byref(gs), ctypes.c_void_p(self.stream.cuda_stream), ctypes.byref(err))
-                elif lp:
-                    q = self._lp_struct(True)
-                    g = self.lib.cain_plan_capture_lp(ctypes.c_void_p(plan), M, ctypes.byref(rs), steps,
-                                                      ctypes.byref(q), ctypes.c_void_p(self.stream.cuda_stream),
-                                                      ctypes.byref(err))
-                else:
-                    g = self.lib.cain_plan_capture(ctypes.c_void_p(plan), M, ctypes.byref(rs), steps,
-                                                   ctypes.c_void_p(self.stream.cuda_stream), ctypes.byref(err))
-            finally:
-                _set_cu_budget(self.lib, 0)
-            if not g:
-                raise RuntimeError(f"hipGraph capture failed (err={err.value})")
-            self._graphs[key] = g
-        return g
+    def _run_graphs(self, M: int, nsteps: int, lp: bool = False, gr: bool = False, st: bool = False,
+                    spec_mode: Optional[int] = None) -> None:
+        """``nsteps`` decode steps over the first ``M`` decode rows, replayed from the cached graphs: chunks of
+        ``steps_per_graph`` steps, then the remainder as one-step graphs.  ``spec_mode`` given: speculative steps."""
+        k, stream_h = self.steps_per_graph, self._stream_h()
+        for n, count in ((k, nsteps // k), (1, nsteps % k)):
+            if not count:
+                continue
+            g = self._graph_spec(M, n, spec_mode) if spec_mode is not None else self._graph(M, n, lp, gr, st)
+            for _ in range(count):
+                rc = self.lib.cain_graph_launch(ctypes.c_void_p(g), stream_h)
+                if rc != 0:
+                    raise RuntimeError(f"hipGraphLaunch failed rc={rc}")
 
     # ---------------------------------------------------------------- speculative decoding
     def _spec_bufs(self) -> Dict:
         """Device buffers of speculative decoding (csrc/spec.h), made when the mode first runs."""
         if self._spec is None:
-            from .. import ops
-
             self._spec = ops.spec_alloc(self.max_batch, self.speculative, self.max_batch, self.T_max, self.cfg.vocab,
                                         self.device)
         return self._spec
@@ -1013,20 +953,8 @@ class DecodeEngine:
     def _spec_draft_bufs(self) -> Dict:
         """Device buffers of draft-model mode (csrc/spec.h CainSpecDraft), made when the mode first runs."""
         if self._specd is None:
-            from .. import ops
-
             self._specd = ops.spec_draft_alloc(self._spec_bufs(), self.draft.cfg.vocab, self.draft.cfg.bos_id)
         return self._specd
-
-    def _spec_model_args(self, B: int):
-        """(target plan, draft plan for 2 B rows, draft plan for B rows, rows, CainSpec in given mode, CainSpecDraft)
-        of a draft-model step over ``B`` sequences."""
-        from .. import ops
-
-        vp = ctypes.c_void_p
-        return (vp(self._plan(B * (self.speculative + 1))), vp(self.draft._plan(2 * B)), vp(self.draft._plan(B)),
-                self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), 1),
-                ops.spec_draft_struct(self._spec_draft_bufs()))
 
     def _spec_stats(self, row: int) -> Dict:
         """Counters of decode row ``row``: drafts proposed, drafts accepted, live steps, tokens per step."""
@@ -1036,61 +964,15 @@ class DecodeEngine:
                     step_tokens=b["step_tokens"][row, :min(n, self.T_max)].cpu().tolist())
 
     def _forward_spec(self, B: int, mode: int) -> None:
-        from .. import ops
-
-        stream_h = ctypes.c_void_p(self.stream.cuda_stream)
-        if self.draft is not None:
-            lib = ops.load_spec_model()
-            plan, d2, d1, rs, sp, sd = self._spec_model_args(B)
-        else:
-            lib = ops.load_spec()
-            rs, sp = self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), mode)
-            plan = self._plan(B * (self.speculative + 1))
-        _set_cu_budget(self.lib, self.cu_limit)
-        try:
-            if self.draft is not None:
-                rc = lib.cain_plan_forward_spec_model(plan, d2, d1, B, ctypes.byref(rs), ctypes.byref(sp),
-                                                      ctypes.byref(sd), stream_h)
-            else:
-                rc = lib.cain_plan_forward_spec(ctypes.c_void_p(plan), B, ctypes.byref(rs), ctypes.byref(sp),
-                                                stream_h)
-        finally:
-            _set_cu_budget(self.lib, 0)
-        if rc != 0:
-            where = self.lib.cain_plan_last_failure()
-            raise RuntimeError(f"cain_plan_forward_spec failed rc={rc}" + (f" at {where.decode()}" if where else ""))
+        step = self._step(B, self.rows, True, True, spec_mode=mode)
+        with self._cu_budget():
+            ops.step_run(step, self._stream_h())
 
     def _graph_spec(self, B: int, steps: int, mode: int) -> int:
         """``steps`` speculative steps (draft -> verify forward over ``B (K + 1)`` rows -> accept) over ``B``
         sequences as one graph; cache entries of their own, beside the plain graphs."""
-        from .. import ops
-
         key = (B, steps, "spec", "draft" if self.draft is not None else mode)
-        g = self._graphs.get(key)
-        if g is None:
-            err = ctypes.c_int(0)
-            stream_h = ctypes.c_void_p(self.stream.cuda_stream)
-            if self.draft is not None:
-                lib = ops.load_spec_model()
-                plan, d2, d1, rs, sp, sd = self._spec_model_args(B)
-            else:
-                lib = ops.load_spec()
-                rs, sp = self._rows_struct(self.rows, True), ops.spec_struct(self._spec_bufs(), mode)
-                plan = self._plan(B * (self.speculative + 1))
-            _set_cu_budget(self.lib, self.cu_limit)
-            try:
-                if self.draft is not None:
-                    g = lib.cain_plan_capture_spec_model(plan, d2, d1, B, ctypes.byref(rs), ctypes.byref(sp),
-                                                         ctypes.byref(sd), steps, stream_h, ctypes.byref(err))
-                else:
-                    g = lib.cain_plan_capture_spec(ctypes.c_void_p(plan), B, ctypes.byref(rs), ctypes.byref(sp),
-                                                   steps, stream_h, ctypes.byref(err))
-            finally:
-                _set_cu_budget(self.lib, 0)
-            if not g:
-                raise RuntimeError(f"hipGraph capture of the speculative steps failed (err={err.value})")
-            self._graphs[key] = g
-        return g
+        return self._captured(key, steps, lambda: self._step(B, self.rows, True, True, spec_mode=mode))
 
     def close(self) -> None:
         if getattr(self, "draft", None) is not None:
@@ -1249,8 +1131,6 @@ class DecodeEngine:
 
     def _generate_hip(self, ids, nps, row_opts, use_graph, on_tokens=None, check_every: int = 1, want=None,
                       drafts=None, fmt=None):
-        from .. import ops
-
         dev = self.device
         B = len(ids)
         with_lp = want is not None and any(w >= 0 for w in want)
@@ -1290,38 +1170,17 @@ class DecodeEngine:
             self.stream.synchronize()
             t1 = time.perf_counter_ns()
             steps = max(nps)
-            stream_h = ctypes.c_void_p(self.stream.cuda_stream)
+            feats = {k: v for k, v in (("lp", lq), ("gr", gq), ("st", sq)) if v is not None}
 
             def launch(nsteps: int) -> None:
-                if spec and not use_graph:
-                    for _ in range(nsteps):
+                if use_graph:
+                    self._run_graphs(B, nsteps, with_lp, with_gr, with_st, spec_mode if spec else None)
+                    return
+                for _ in range(nsteps):
+                    if spec:
                         self._forward_spec(B, spec_mode)
-                    return
-                if not use_graph:
-                    for _ in range(nsteps):
-                        if sq is not None:
-                            self._forward(B, r, want_logits=True, want_sample=True, lp=lq, gr=gq, st=sq)
-                        elif gq is not None:
-                            self._forward(B, r, want_logits=True, want_sample=True, lp=lq, gr=gq)
-                        elif lq is None:  # (the call it always was: wrappers of _forward see the same arguments)
-                            self._forward(B, r, want_logits=True, want_sample=True)
-                        else:
-                            self._forward(B, r, want_logits=True, want_sample=True, lp=lq)
-                    return
-                k = self.steps_per_graph
-                graph = (lambda n: self._graph_spec(B, n, spec_mode)) if spec else \
-                    (lambda n: self._graph(B, n, with_lp, with_gr, True)) if with_st else \
-                    (lambda n: self._graph(B, n, with_lp, with_gr) if with_gr else self._graph(B, n, with_lp))
-                g = graph(k) if nsteps >= k else None
-                for _ in range(nsteps // k):
-                    rc = self.lib.cain_graph_launch(ctypes.c_void_p(g), stream_h)
-                    if rc != 0:
-                        raise RuntimeError(f"hipGraphLaunch failed rc={rc}")
-                if nsteps % k:
-                    g1 = graph(1)
-                    for _ in range(nsteps % k):
-                        if self.lib.cain_graph_launch(ctypes.c_void_p(g1), stream_h) != 0:
-                            raise RuntimeError("hipGraphLaunch failed")
+                    else:  # (without a feature, the call it always was: wrappers of _forward see the same arguments)
+                        self._forward(B, r, want_logits=True, want_sample=True, **feats)
 
             # first token on its own so time-to-first-token is measured exactly
             launch(1)
@@ -1709,8 +1568,6 @@ class ContinuousBatch:
         request, or the option key ``"format"``): a JSON-mode row's automaton state starts fresh here and moves with
         the row (``json_state(row)`` reads how it stands).  ``options[i]["stop"]``: the request's stop strings, as
         ``generate``'s (``stop_hit(row)`` reads whether one ended the row)."""
-        from .. import ops
-
         eng = self.eng
         k = len(prompts)
         if k == 0:
@@ -1755,12 +1612,9 @@ class ContinuousBatch:
         with torch.cuda.stream(eng.stream):
             if copies:  # every donor's prefix in one launch, before any prefill of this call writes a slot
                 cfg = eng.cfg
-                _set_cu_budget(eng.lib, eng.cu_limit)
-                try:
+                with eng._cu_budget():
                     rc = ops.kv_copy_prefix(eng.kcache, eng.vtcache, cfg.n_layers, eng.max_batch, cfg.n_kv_heads,
                                             cfg.head_dim, eng.T_max, copies, stream=eng.stream)
-                finally:
-                    _set_cu_budget(eng.lib, 0)
                 if rc != 0:
                     raise RuntimeError(f"cain_kv_copy_prefix refused {copies} (rc={rc})")
             eng._prefill(ids, slots, start)
@@ -1803,28 +1657,13 @@ class ContinuousBatch:
         if self.n == 0:
             return
         steps = steps or eng.steps_per_graph
-        stream_h = ctypes.c_void_p(eng.stream.cuda_stream)
         for i in range(self.n):
             self._steps[i] += steps
-        with_lp = any(w >= 0 for w in self.want)  # some live row wants logprobs: the graphs that compute them
-        # speculative engines: each step drafts (n-gram lookup), verifies K + 1 rows per live row and commits
-        with_gr = any(self.fmt)  # some live row is in JSON mode: the graphs with the mask and the advance
-        with_st = any(self.stops)  # some live row has stop strings: the graphs with the match after the sampler
-        graph = (lambda n: eng._graph_spec(self.n, n, 0)) if eng.speculative else \
-            (lambda n: eng._graph(self.n, n, with_lp, with_gr, True)) if with_st else \
-            (lambda n: eng._graph(self.n, n, with_lp, with_gr) if with_gr else eng._graph(self.n, n, with_lp))
         with torch.cuda.stream(eng.stream):
-            k = eng.steps_per_graph
-            if steps >= k:
-                g = graph(k)
-                for _ in range(steps // k):
-                    if eng.lib.cain_graph_launch(ctypes.c_void_p(g), stream_h) != 0:
-                        raise RuntimeError("hipGraphLaunch failed")
-            if steps % k:
-                g1 = graph(1)
-                for _ in range(steps % k):
-                    if eng.lib.cain_graph_launch(ctypes.c_void_p(g1), stream_h) != 0:
-                        raise RuntimeError("hipGraphLaunch failed")
+            # the graphs with the logprobs, JSON mode's mask and advance, the stop match: where some live row wants
+            # them; speculative engines: each step drafts (n-gram lookup), verifies K + 1 rows per live row and commits
+            eng._run_graphs(self.n, steps, any(w >= 0 for w in self.want), any(self.fmt), any(self.stops),
+                            0 if eng.speculative else None)
 
     def spec_stats(self, row: int) -> Optional[Dict]:
         """Speculative counters of a live row (``GenResult``'s fields of that name); None when the mode is off."""
@@ -1918,8 +1757,6 @@ class ContinuousBatch:
                 h64 = r["hist"].view(-1, 64)
                 h64[dst] = h64[src]
                 eng.gen[dst] = eng.gen[src]
-                from .. import ops
-
                 sp = eng.sample_params.view(-1, ops.SAMPLE_BYTES)
                 sp[dst] = sp[src]
                 if eng._lp is not None:

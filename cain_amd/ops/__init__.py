@@ -67,12 +67,83 @@ class CainGemm(ctypes.Structure):
                 + [(f, ctypes.c_int) for f in ("H", "Hkv", "hd", "T_max", "epi", "fmt", "tile0", "waves")])
 
 
-_lib: Optional[ctypes.CDLL] = None
-_lock = threading.Lock()
-
 vp = ctypes.c_void_p
 ci = ctypes.c_int
 cf = ctypes.c_float
+
+# ---- the records of a plan and of its step (csrc/cain_api.h, csrc/spec.h; CainLayer / CainPlanDesc: csrc/runtime.hip)
+LAYER_FIELDS = ("wqkv", "bqkv", "wo", "wgu", "wdown", "sqkv", "so", "sgu", "sdown", "wqkv8", "wo8", "wgu8", "wdown8")
+LAYER_FORMATS = ("fqkv", "fo", "fgu", "fdown")  # per-matrix format ids of a GGUF plan, then the split V
+
+
+class CainLayer(ctypes.Structure):
+    _fields_ = [(n, vp) for n in LAYER_FIELDS] + [(n, ci) for n in LAYER_FORMATS] + [("wv", vp), ("sv", vp)]
+
+
+class CainPlanDesc(ctypes.Structure):
+    _fields_ = ([(n, ci) for n in ("n_layers", "d", "H", "Hkv", "hd", "ffn", "V", "act_kind", "T_max", "Mpad", "nsplit",
+                                   "waves")]
+                + [(n, cf) for n in ("eps", "embed_scale", "attn_scale")]
+                + [(n, vp) for n in ("embed", "lm_head", "layers", "kcache", "vtcache")]
+                + [("kv_layer_elems", ctypes.c_longlong)]
+                + [(n, vp) for n in ("cos_t", "sin_t", "x", "q", "attn", "act", "logits", "part_o", "part_ml",
+                                     "counters", "gemm_ws")]
+                + [("gemm_ws_bytes", ctypes.c_longlong), ("wfmt", ci), ("lm_head_scale", vp), ("kv8", ci),
+                   ("lm_head8", vp), ("x8", vp), ("xs", vp), ("x8_ld", ci), ("q4_gain", ci), ("flm_head", ci)])
+
+
+class CainRows(ctypes.Structure):
+    _fields_ = ([(n, vp) for n in ("tok", "pos", "slot", "n_gen", "max_new", "done", "hist", "gen")]
+                + [("ldg", ci), ("sample_params", vp)])
+
+
+class CainLogprob(ctypes.Structure):
+    _fields_ = [("topn", vp), ("nmax", ci), ("lp", vp), ("top_id", vp), ("top_lp", vp), ("keep", vp), ("target", vp)]
+
+
+class CainGrammar(ctypes.Structure):
+    _fields_ = [("gram_on", vp), ("gstate", vp), ("piece_off", vp), ("piece_bytes", vp)]
+
+
+class CainStop(ctypes.Structure):
+    _fields_ = [("stop_on", vp), ("sstate", vp), ("stop_len", vp), ("stop_bytes", vp), ("piece_off", vp),
+                ("piece_bytes", vp)]
+
+
+_SPEC_INTS = ("K", "mode", "slots", "lds", "ldv", "ldt", "vocab", "ldg")
+_SPEC_PTRS = ("seq", "given", "x_tok", "x_pos", "x_slot", "x_n_gen", "x_max_new", "x_done", "x_hist", "x_gen",
+              "x_params", "nd", "draft", "drafted", "accepted", "n_step", "step_tokens")
+_SPECD_INTS = ("K", "dvocab", "dbos", "slots", "lds", "ldv", "ldg", "pad_")
+_SPECD_PTRS = ("seq", "given", "dvalid", "p0", "nd", "r_tok", "r_pos", "r_slot", "r_n_gen", "r_max_new", "r_done",
+               "r_hist", "r_gen", "r_params")
+
+
+class CainSpec(ctypes.Structure):
+    _fields_ = [(n, ci) for n in _SPEC_INTS] + [(n, vp) for n in _SPEC_PTRS]
+
+
+class CainSpecDraft(ctypes.Structure):
+    _fields_ = [(n, ci) for n in _SPECD_INTS] + [(n, vp) for n in _SPECD_PTRS]
+
+
+class CainStep(ctypes.Structure):
+    """The call record of ``cain_step_run`` / ``cain_step_capture`` (csrc/cain_api.h CainStep, which says what the
+    entries refuse).  It holds raw pointers to the other records: whoever fills it keeps those objects alive."""
+    _fields_ = ([("plan", vp), ("draft2", vp), ("draft1", vp), ("rows", ctypes.POINTER(CainRows)),
+                 ("lp", ctypes.POINTER(CainLogprob)), ("gr", ctypes.POINTER(CainGrammar)),
+                 ("st", ctypes.POINTER(CainStop)), ("spec", ctypes.POINTER(CainSpec)),
+                 ("spec_draft", ctypes.POINTER(CainSpecDraft))]
+                + [(n, ci) for n in ("M", "want_logits", "want_sample")])
+
+
+# the native size entry of every record
+_RECORD_SIZES = ((CainGemm, "cain_gemm_size"), (CainLayer, "cain_layer_size"), (CainPlanDesc, "cain_plan_desc_size"),
+                 (CainRows, "cain_rows_size"), (CainLogprob, "cain_logprob_size"), (CainGrammar, "cain_grammar_size"),
+                 (CainStop, "cain_stop_size"), (CainSpec, "cain_spec_size"), (CainSpecDraft, "cain_spec_draft_size"),
+                 (CainStep, "cain_step_size"))
+
+_lib: Optional[ctypes.CDLL] = None
+_lock = threading.Lock()
 
 
 def load() -> ctypes.CDLL:
@@ -96,10 +167,16 @@ def load() -> ctypes.CDLL:
         if int(real.cain_sample_params_size()) != SAMPLE_BYTES:  # also an A/B build from an older source
             raise NativeOpsUnavailable(f"{LIB_PATH} packs {int(real.cain_sample_params_size())}-byte sampling "
                                        f"options, this package {SAMPLE_BYTES}: rebuild (python -m cain_amd.build)")
-        # (a build from before the record has no GEMM entry of these names: plan-level A/B runs only)
-        if hasattr(real, "cain_gemm_size") and int(real.cain_gemm_size()) != ctypes.sizeof(CainGemm):
-            raise NativeOpsUnavailable(f"{LIB_PATH} takes a {int(real.cain_gemm_size())}-byte GEMM call record, this "
-                                       f"package fills {ctypes.sizeof(CainGemm)}: rebuild (python -m cain_amd.build)")
+        # every record's size, and the sizes and limits of the kernels' per-row states (a build from before a record
+        # has no size entry for it and no entry that takes it: a call fails by name)
+        sizes = [(rec.__name__, entry, ctypes.sizeof(rec)) for rec, entry in _RECORD_SIZES] + [
+            ("JSON_STATE_BYTES", "cain_json_state_size", JSON_STATE_BYTES),
+            ("STOP_STATE_BYTES", "cain_stop_state_size", STOP_STATE_BYTES), ("STOP_MAX", "cain_stop_max", STOP_MAX),
+            ("STOP_LEN_MAX", "cain_stop_len_max", STOP_LEN_MAX)]
+        for name, entry, mine in sizes:
+            if hasattr(real, entry) and int(getattr(real, entry)()) != mine:
+                raise NativeOpsUnavailable(f"{LIB_PATH}: {name} is {int(getattr(real, entry)())}, this package's is "
+                                           f"{mine}: rebuild (python -m cain_amd.build)")
         for entry in ("bf16", "fp8", "mxfp4", "gguf", "fp8a8", "mxfp4a8"):
             getattr(lib, "cain_gemm_" + entry).argtypes = [ctypes.POINTER(CainGemm), vp]
         lib.cain_gemm_w4_ws_bytes.restype = ctypes.c_longlong
@@ -155,10 +232,10 @@ def load() -> ctypes.CDLL:
         lib.cain_plan_create.restype = vp
         lib.cain_plan_create.argtypes = [vp]
         lib.cain_plan_destroy.argtypes = [vp]
-        lib.cain_plan_forward.argtypes = [vp, ci, vp, ci, ci, vp]
         lib.cain_plan_last_failure.restype = ctypes.c_char_p
-        lib.cain_plan_capture.restype = vp
-        lib.cain_plan_capture.argtypes = [vp, ci, vp, ci, vp, ctypes.POINTER(ci)]
+        lib.cain_step_run.argtypes = [ctypes.POINTER(CainStep), vp]
+        lib.cain_step_capture.restype = vp
+        lib.cain_step_capture.argtypes = [ctypes.POINTER(CainStep), ci, vp, ctypes.POINTER(ci)]
         lib.cain_graph_launch.argtypes = [vp, vp]
         lib.cain_graph_destroy.argtypes = [vp]
         lib.cain_set_cu_budget.argtypes = [ci]
@@ -172,9 +249,14 @@ def load() -> ctypes.CDLL:
         lib.cain_logprob_chosen.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp, vp]
         lib.cain_logprob_keep_bytes.restype = ctypes.c_longlong
         lib.cain_logprob_keep_bytes.argtypes = [ci]
-        lib.cain_plan_forward_lp.argtypes = [vp, ci, vp, ci, ci, vp, vp]
-        lib.cain_plan_capture_lp.restype = vp
-        lib.cain_plan_capture_lp.argtypes = [vp, ci, vp, ci, vp, vp, ctypes.POINTER(ci)]
+        lib.cain_json_mask.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+        lib.cain_json_advance.argtypes = [ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        lib.cain_stop_advance.argtypes = [ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.cain_spec_draft.argtypes = [vp, ci, ci] + [vp] * 9
+        lib.cain_spec_accept.argtypes = [vp, ci, ci] + [vp] * 8 + [ci, vp, vp]
+        lib.cain_spec_model_rows.argtypes = [vp, ci, ci] + [vp] * 9
+        lib.cain_spec_model_next.argtypes = [vp, ci, ci, ci, vp, vp, vp]
+        lib.cain_spec_dvalid.argtypes = [vp, ci, ci, vp, vp, vp]
         if os.environ.get("CAIN_WGEMM_INLINE") and hasattr(real, "cain_wgemm_set_inline"):  # A/B runs
             real.cain_wgemm_set_inline(int(os.environ["CAIN_WGEMM_INLINE"]))
         if os.environ.get("CAIN_SAMPLE_CM"):  # A/B runs (set_sample_cm)
@@ -219,6 +301,25 @@ def _stream():
 def _check(rc: int, what: str) -> None:
     if rc != 0:
         raise RuntimeError(f"{what} failed (rc={rc})")
+
+
+def step_run(step: CainStep, stream) -> None:
+    """Enqueue one step (``cain_step_run``) on ``stream`` (a native handle)."""
+    lib = load()
+    rc = lib.cain_step_run(ctypes.byref(step), stream)
+    if rc != 0:
+        where = lib.cain_plan_last_failure()
+        raise RuntimeError(f"cain_step_run failed rc={rc}" + (f" at {where.decode()}" if where else ""))
+
+
+def step_capture(step: CainStep, steps: int, stream) -> int:
+    """``steps`` such steps recorded on ``stream`` into one executable graph (``cain_step_capture``): its handle, for
+    ``cain_graph_launch`` / ``cain_graph_destroy``."""
+    err = ctypes.c_int(0)
+    g = load().cain_step_capture(ctypes.byref(step), int(steps), stream, ctypes.byref(err))
+    if not g:
+        raise RuntimeError(f"hipGraph capture failed (err={err.value})")
+    return g
 
 
 def _gpu(*ts):
@@ -907,27 +1008,6 @@ JSON_STATE_BYTES = 16  # sizeof(JsonState): control word, depth word, 64-bit bra
 JSON_VOCAB_MAX = 1 << 23  # a masked logit carries its token id in the mantissa
 
 
-class CainGrammar(ctypes.Structure):  # csrc/runtime.hip CainGrammar
-    _fields_ = [("gram_on", vp), ("gstate", vp), ("piece_off", vp), ("piece_bytes", vp)]
-
-
-def load_grammar() -> ctypes.CDLL:
-    """``load()`` with JSON mode's entry points' signatures set (a library without them: AttributeError)."""
-    lib = load()
-    if not getattr(lib, "_cain_grammar_sig", False):
-        lib.cain_json_mask.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
-        lib.cain_json_advance.argtypes = [ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]
-        lib.cain_plan_forward_gr.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp]
-        lib.cain_plan_capture_gr.restype = vp
-        lib.cain_plan_capture_gr.argtypes = [vp, ci, vp, ci, vp, vp, vp, ctypes.POINTER(ci)]
-        if int(lib.cain_json_state_size()) != JSON_STATE_BYTES or \
-                int(lib.cain_grammar_size()) != ctypes.sizeof(CainGrammar):
-            raise NativeOpsUnavailable(f"{LIB_PATH}: JSON-mode records differ from this package's: rebuild "
-                                       f"(python -m cain_amd.build)")
-        lib._cain_grammar_sig = True
-    return lib
-
-
 def json_table(pieces, device) -> dict:
     """The vocabulary of JSON mode on the device: ``pieces[t]`` is the bytes token ``t`` appends (empty: a special
     token, never allowed).  Returns ``dict(V, piece_off [V + 1] int32, piece_bytes uint8)``."""
@@ -963,7 +1043,7 @@ def json_mask(logits: torch.Tensor, V: int, gram_on, done, gstate, table: dict, 
     each token whose bytes cannot continue the row's JSON document from ``gstate[m]`` gets the logit
     ``-(2^100 (1 + t / 2^23))``; accepted tokens and other rows are not written.  ``cmax [M, V / 16]``: the rows'
     16-column chunk maxima, rewritten from the masked logits.  Returns the entry's code (non-zero: refused)."""
-    lib = load_grammar()
+    lib = load()
     _gpu(logits, gram_on, done, gstate, table["piece_off"], table["piece_bytes"], cmax)
     assert logits.dtype == torch.float32 and logits.stride(1) == 1 and gstate.is_contiguous()
     assert gram_on.dtype == torch.int32 and done.dtype == torch.int32 and int(V) <= table["V"]
@@ -976,7 +1056,7 @@ def json_advance(gram_on, gen: torch.Tensor, n_gen, done, gstate, table: dict) -
     """AFTER the sampler: every JSON-mode row that generated a token this step consumes it (``gen[m, n_gen[m] - 1]``);
     a closed top-level object sets ``done[m]``, an invalid token is taken back (``n_gen[m] -= 1``), fails the state
     and sets ``done[m]``."""
-    lib = load_grammar()
+    lib = load()
     _gpu(gram_on, gen, n_gen, done, gstate)
     assert gen.dtype == torch.int32 and gen.stride(1) == 1 and gstate.is_contiguous()
     return int(lib.cain_json_advance(gen.shape[0], int(table["V"]), _p(gram_on), _p(gen), gen.stride(0), _p(n_gen),
@@ -988,27 +1068,6 @@ def json_advance(gram_on, gen: torch.Tensor, n_gen, done, gstate, table: dict) -
 STOP_STATE_BYTES = 48  # sizeof(StopState): 32 tail bytes, tokens, bytes, hit_start, hit_which
 STOP_MAX = 8
 STOP_LEN_MAX = 32
-
-
-class CainStop(ctypes.Structure):  # csrc/runtime.hip CainStop
-    _fields_ = [("stop_on", vp), ("sstate", vp), ("stop_len", vp), ("stop_bytes", vp), ("piece_off", vp),
-                ("piece_bytes", vp)]
-
-
-def load_stop() -> ctypes.CDLL:
-    """``load()`` with the stop sequences' entry points' signatures set (a library without them: AttributeError)."""
-    lib = load()
-    if not getattr(lib, "_cain_stop_sig", False):
-        lib.cain_stop_advance.argtypes = [ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.cain_plan_forward_st.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp]
-        lib.cain_plan_capture_st.restype = vp
-        lib.cain_plan_capture_st.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, ctypes.POINTER(ci)]
-        if int(lib.cain_stop_state_size()) != STOP_STATE_BYTES or int(lib.cain_stop_size()) != ctypes.sizeof(CainStop) \
-                or int(lib.cain_stop_max()) != STOP_MAX or int(lib.cain_stop_len_max()) != STOP_LEN_MAX:
-            raise NativeOpsUnavailable(f"{LIB_PATH}: stop-sequence records differ from this package's: rebuild "
-                                       f"(python -m cain_amd.build)")
-        lib._cain_stop_sig = True
-    return lib
 
 
 def stop_table_host(rows_of_strings):
@@ -1060,7 +1119,7 @@ def stop_advance(stop_on, gen: torch.Tensor, n_gen, done, sstate, stop_len, stop
     step (``n_gen[m]`` is one above the tokens its state has consumed) consumes ``gen[m, n_gen[m] - 1]``; a stop string
     that ends inside the token's bytes sets ``done[m]`` and the state's ``hit_start`` / ``hit_which``.  Returns the
     entry's code (non-zero: refused)."""
-    lib = load_stop()
+    lib = load()
     _gpu(stop_on, gen, n_gen, done, sstate, stop_len, stop_bytes, table["piece_off"], table["piece_bytes"])
     assert gen.dtype == torch.int32 and gen.stride(1) == 1 and sstate.is_contiguous()
     assert stop_len.is_contiguous() and stop_bytes.is_contiguous() and stop_len.dtype == torch.int32
@@ -1087,13 +1146,6 @@ def _sample_ws(device, nbytes: int) -> torch.Tensor:
 # ------------------------------------------------------------ speculative decoding (csrc/spec.hip)
 SPEC_K_MAX = 7  # csrc/spec.h
 ROW_KEYS = ("tok", "pos", "slot", "n_gen", "max_new", "done", "hist")
-_SPEC_INTS = ("K", "mode", "slots", "lds", "ldv", "ldt", "vocab", "ldg")
-_SPEC_PTRS = ("seq", "given", "x_tok", "x_pos", "x_slot", "x_n_gen", "x_max_new", "x_done", "x_hist", "x_gen",
-              "x_params", "nd", "draft", "drafted", "accepted", "n_step", "step_tokens")
-
-
-class CainSpec(ctypes.Structure):  # csrc/spec.h CainSpec
-    _fields_ = [(n, ci) for n in _SPEC_INTS] + [(n, vp) for n in _SPEC_PTRS]
 
 
 def spec_alloc(R: int, K: int, slots: int, T_max: int, vocab: int, device) -> dict:
@@ -1124,30 +1176,9 @@ def spec_struct(spec: dict, mode: int) -> CainSpec:
     return s
 
 
-def _spec_sig(lib) -> None:
-    if getattr(lib, "_cain_spec_sig", False):
-        return
-    lib.cain_spec_draft.argtypes = [vp, ci, ci] + [vp] * 9
-    lib.cain_spec_accept.argtypes = [vp, ci, ci] + [vp] * 8 + [ci, vp, vp]
-    lib.cain_plan_forward_spec.argtypes = [vp, ci, vp, vp, vp]
-    lib.cain_plan_capture_spec.restype = vp
-    lib.cain_plan_capture_spec.argtypes = [vp, ci, vp, vp, ci, vp, ctypes.POINTER(ci)]
-    if int(lib.cain_spec_size()) != ctypes.sizeof(CainSpec):
-        raise NativeOpsUnavailable(f"{LIB_PATH}: CainSpec is {int(lib.cain_spec_size())} bytes, this package packs "
-                                   f"{ctypes.sizeof(CainSpec)}: rebuild (python -m cain_amd.build)")
-    lib._cain_spec_sig = True
-
-
-def load_spec() -> ctypes.CDLL:
-    """``load()`` with the speculative entry points' signatures set (a library without them: AttributeError)."""
-    lib = load()
-    _spec_sig(lib)
-    return lib
-
-
 def spec_draft(rows: dict, params: torch.Tensor, spec: dict, R: int, mode: int, T_max: int) -> None:
     """Draft for sequences ``[0, R)`` of the decode rows (``ROW_KEYS`` tensors) and write the expanded state."""
-    lib = load_spec()
+    lib = load()
     _gpu(params, *[rows[k] for k in ROW_KEYS])
     assert spec["nd"].shape[0] >= R and rows["tok"].shape[0] >= R
     s = spec_struct(spec, mode)
@@ -1157,7 +1188,7 @@ def spec_draft(rows: dict, params: torch.Tensor, spec: dict, R: int, mode: int, 
 
 def spec_accept(rows: dict, gen: torch.Tensor, params: torch.Tensor, spec: dict, R: int, T_max: int) -> None:
     """Commit, per sequence, the tokens the sampler left in ``spec["x_tok"]`` that the step's drafts allow."""
-    lib = load_spec()
+    lib = load()
     _gpu(params, gen, *[rows[k] for k in ROW_KEYS])
     s = spec_struct(spec, 0)
     r = rows
@@ -1173,14 +1204,7 @@ def _np(t):
 
 
 # ---- draft-model mode (csrc/spec.h CainSpecDraft)
-_SPECD_INTS = ("K", "dvocab", "dbos", "slots", "lds", "ldv", "ldg", "pad_")
-_SPECD_PTRS = ("seq", "given", "dvalid", "p0", "nd", "r_tok", "r_pos", "r_slot", "r_n_gen", "r_max_new", "r_done",
-               "r_hist", "r_gen", "r_params")
 _SPECD_ROWS = ("r_tok", "r_pos", "r_slot", "r_n_gen", "r_max_new", "r_done")
-
-
-class CainSpecDraft(ctypes.Structure):  # csrc/spec.h CainSpecDraft
-    _fields_ = [(n, ci) for n in _SPECD_INTS] + [(n, vp) for n in _SPECD_PTRS]
 
 
 def spec_draft_alloc(spec: dict, dvocab: int, dbos: int) -> dict:
@@ -1206,26 +1230,9 @@ def spec_draft_struct(sd: dict) -> CainSpecDraft:
     return s
 
 
-def load_spec_model() -> ctypes.CDLL:
-    """``load_spec()`` with the draft-model entry points' signatures set."""
-    lib = load_spec()
-    if not getattr(lib, "_cain_spec_model_sig", False):
-        lib.cain_spec_model_rows.argtypes = [vp, ci, ci] + [vp] * 9
-        lib.cain_spec_model_next.argtypes = [vp, ci, ci, ci, vp, vp, vp]
-        lib.cain_spec_dvalid.argtypes = [vp, ci, ci, vp, vp, vp]
-        lib.cain_plan_forward_spec_model.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp]
-        lib.cain_plan_capture_spec_model.restype = vp
-        lib.cain_plan_capture_spec_model.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, vp, ctypes.POINTER(ci)]
-        if int(lib.cain_spec_draft_size()) != ctypes.sizeof(CainSpecDraft):
-            raise NativeOpsUnavailable(f"{LIB_PATH}: CainSpecDraft is {int(lib.cain_spec_draft_size())} bytes, this "
-                                       f"package packs {ctypes.sizeof(CainSpecDraft)}: rebuild (python -m cain_amd.build)")
-        lib._cain_spec_model_sig = True
-    return lib
-
-
 def spec_model_rows(rows: dict, params: torch.Tensor, sd: dict, R: int, T_max: int) -> None:
     """The 2 R rows of the first draft forward from sequences ``[0, R)`` of the decode rows."""
-    lib = load_spec_model()
+    lib = load()
     _gpu(params, *[rows[k] for k in ROW_KEYS])
     assert sd["nd"].shape[0] >= R and rows["tok"].shape[0] >= R
     s = spec_draft_struct(sd)
@@ -1235,7 +1242,7 @@ def spec_model_rows(rows: dict, params: torch.Tensor, sd: dict, R: int, T_max: i
 
 def spec_model_next(rows: dict, sd: dict, R: int, j: int, T_max: int) -> None:
     """After draft forward ``j``'s sampler: ``d_j`` into ``given``, the rows of forward ``j + 1``."""
-    lib = load_spec_model()
+    lib = load()
     s = spec_draft_struct(sd)
     _check(lib.cain_spec_model_next(ctypes.byref(s), R, j, T_max, _p(rows["slot"]), _p(rows["n_gen"]), _stream()),
            "spec_model_next")
@@ -1243,7 +1250,7 @@ def spec_model_next(rows: dict, sd: dict, R: int, j: int, T_max: int) -> None:
 
 def spec_dvalid(rows: dict, sd: dict, R: int, T_max: int) -> None:
     """After accept: ``dvalid`` of the sequences' slots from their new positions."""
-    lib = load_spec_model()
+    lib = load()
     s = spec_draft_struct(sd)
     _check(lib.cain_spec_dvalid(ctypes.byref(s), R, T_max, _p(rows["slot"]), _p(rows["pos"]), _stream()),
            "spec_dvalid")

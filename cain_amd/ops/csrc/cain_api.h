@@ -1,6 +1,7 @@
 // The C API of libcain_kernels.so that crosses a file boundary: every entry point one .hip file defines and another
 // calls, declared once (host-only declarations; common.h includes this header, so each definition is checked against
-// its prototype), and CainGemm, the one call record of every GEMM entry (ops/__init__.py mirrors it in ctypes).
+// its prototype), CainGemm, the one call record of every GEMM entry, and CainStep, the one call record of a plan's
+// step, with the records it points to (ops/__init__.py mirrors them in ctypes).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -47,7 +48,80 @@ struct CainGemm {
   int waves;  // bf16 skinny kernel: waves per workgroup (0: the rule)
 };
 
+// The rows of a forward (runtime.hip): decode -- one row per live sequence; prefill -- one row per prompt token.
+struct CainRows {
+  int* tok;
+  int* pos;
+  int* slot;
+  // sampling state (decode rows only; may be null for prefill)
+  int* n_gen;
+  const int* max_new;
+  int* done;
+  int* hist;
+  int* gen;
+  int ldg;
+  const void* sample_params;
+};
+
+// Token log-probabilities of a forward (logprob.hip; CainStep::lp).  Decode forwards (want_sample): the statistics
+// and the top-n run between the LM head and the sampler, the sampled token's logprob after it, into rings indexed
+// like CainRows::gen: lp[m * ldg + n], top_id / top_lp[(m * ldg + n) * 20 + j].
+// Forwards with logits but no sampler (teacher forcing): `target` names each row's token, results are per row:
+// lp[m], top_id / top_lp[m * 20 + j].
+struct CainLogprob {
+  const int* topn;  // per row: -1 not wanted, else how many alternatives (0 .. 20)
+  int nmax;         // the largest of them
+  float* lp;
+  int* top_id;
+  float* top_lp;
+  void* keep;         // decode: cain_logprob_keep_bytes(M) of scratch between the two launches
+  const int* target;  // teacher forcing
+};
+
+// JSON mode of a decode forward (grammar.hip; CainStep::gr): the mask runs between the LM head (after
+// cain_logprob_pre: logprobs stay the model's own distribution) and the sampler, the state advances after it.
+struct CainGrammar {
+  const int* gram_on;          // per row: 0 off, else the row is in JSON mode
+  void* gstate;                // per row: 16 bytes of JsonState (json_pda.h)
+  const int* piece_off;        // [V + 1]: token t's bytes are piece_bytes[piece_off[t] .. piece_off[t + 1])
+  const uint8_t* piece_bytes;
+};
+
+// Stop sequences of a decode forward (stopseq.hip; CainStep::st): the match runs after the sampler, and after JSON
+// mode's advance where that is on too (a token it took back is not consumed).
+struct CainStop {
+  const int* stop_on;          // per row: 0 off, else the row has stop strings
+  void* sstate;                // per row: 48 bytes of StopState (stop_match.h)
+  const int32_t* stop_len;     // [M][8]: bytes of each string, 0 for an unused entry
+  const uint8_t* stop_bytes;   // [M][8][32]
+  const int* piece_off;        // the piece table, as CainGrammar's
+  const uint8_t* piece_bytes;
+};
+
+// One step of a plan, the call record of cain_step_run (enqueue it once) and cain_step_capture (record `steps` of
+// them into one graph): a forward over M rows -- with `spec`, a speculative step over M sequences (spec.h).  A null
+// feature record leaves the launches exactly those of a step without the feature.  What runtime.hip step_ok refuses
+// is refused with -1 before any HIP call.
+struct CainStep {
+  void* plan;    // cain_plan_create
+  void* draft2;  // spec_draft: the draft model's plans for forwards of 2 M and of M rows (null otherwise)
+  void* draft1;
+  const CainRows* rows;
+  const CainLogprob* lp;  // needs want_logits
+  const CainGrammar* gr;  // needs want_logits, want_sample and the rows' sampling state
+  const CainStop* st;     // likewise
+  const CainSpec* spec;   // draft -> forward over M (K + 1) expanded rows -> accept; not with lp / gr / st
+  const CainSpecDraft* spec_draft;  // with `spec` in given mode: the draft model proposes the drafts
+  int M;
+  int want_logits, want_sample;  // a speculative step and every captured step: both 1
+};
+
 }  // extern "C"
+
+// ---- the step (runtime.hip)
+CAIN_API int cain_step_size();
+CAIN_API int cain_step_run(const CainStep* s, hipStream_t st);
+CAIN_API void* cain_step_capture(const CainStep* s, int steps, hipStream_t st, int* err);
 
 // ---- GEMMs (gemm.hip, gemm_w8.hip, gemm_w4.hip, gemm_qstream.hip, wgemm8.hip, wgemm.hip)
 CAIN_API int cain_gemm_size();

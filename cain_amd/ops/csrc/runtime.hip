@@ -2,16 +2,20 @@
 // hipGraph capture/replay.
 //
 // The Python engine owns every buffer (torch allocations on the GPU) and hands
-// the raw pointers over once in a PlanDesc.  `cain_plan_forward` enqueues one
-// forward over M rows (decode: one row per live sequence; prefill: one row per
-// prompt token, each with its own cache slot and position):
+// the raw pointers over once in a PlanDesc.  Every step crosses the C boundary
+// as one record, CainStep (cain_api.h): the plan, the rows and, each null when
+// off, the records of the decode-time features (token log-probabilities, JSON
+// mode, stop sequences, speculative decoding with or without a draft model).
+// `cain_step_run` enqueues one step: a forward over M rows (decode: one row per
+// live sequence; prefill: one row per prompt token, each with its own cache slot
+// and position):
 //
 //   embed -> L x [QKV GEMM(+RMSNorm, +bias, RoPE, KV append)
 //                 -> attention(+split combine) -> O GEMM(+residual)
 //                 -> gate/up GEMM(+RMSNorm, act*mul) -> down GEMM(+residual)]
 //                 -> LM-head GEMM(+RMSNorm) -> sample
 //
-// = 5 launches per layer (the unfused schedule had 9).  `cain_plan_capture` records `steps` consecutive
+// = 5 launches per layer (the unfused schedule had 9).  `cain_step_capture` records `steps` consecutive
 // decode steps into ONE hipGraph; since the sampler advances tok/pos/n_gen on
 // the device, a whole generation is a handful of graph launches with no host
 // round trip per token (graph-replay floor instead of ~290 host launches per
@@ -96,56 +100,6 @@ struct CainPlanDesc {
   // WFMT_Q4_*: 1 when each norm-fed weight's scale buffer ends with its fp32 RMSNorm gain (weights not gain-folded)
   int q4_gain;
   int flm_head;  // WFMT_Q4_* plans: the LM head's format (MFMT_*; 0: the plan's)
-};
-
-struct CainRows {
-  int* tok;
-  int* pos;
-  int* slot;
-  // sampling state (decode rows only; may be null for prefill)
-  int* n_gen;
-  const int* max_new;
-  int* done;
-  int* hist;
-  int* gen;
-  int ldg;
-  const void* sample_params;
-};
-
-// Token log-probabilities of a forward (logprob.hip; cain_plan_forward_lp / cain_plan_capture_lp).  Decode forwards
-// (want_sample): the statistics and the top-n run between the LM head and the sampler, the sampled token's logprob
-// after it, into rings indexed like CainRows::gen: lp[m * ldg + n], top_id / top_lp[(m * ldg + n) * 20 + j].
-// Forwards with logits but no sampler (teacher forcing): `target` names each row's token, results are per row:
-// lp[m], top_id / top_lp[m * 20 + j].
-struct CainLogprob {
-  const int* topn;  // per row: -1 not wanted, else how many alternatives (0 .. 20)
-  int nmax;         // the largest of them
-  float* lp;
-  int* top_id;
-  float* top_lp;
-  void* keep;         // decode: cain_logprob_keep_bytes(M) of scratch between the two launches
-  const int* target;  // teacher forcing
-};
-
-// JSON mode of a decode forward (grammar.hip; cain_plan_forward_gr / cain_plan_capture_gr): the mask runs between the
-// LM head (after cain_logprob_pre: logprobs stay the model's own distribution) and the sampler, the state advances
-// after it.
-struct CainGrammar {
-  const int* gram_on;          // per row: 0 off, else the row is in JSON mode
-  void* gstate;                // per row: 16 bytes of JsonState (json_pda.h)
-  const int* piece_off;        // [V + 1]: token t's bytes are piece_bytes[piece_off[t] .. piece_off[t + 1])
-  const uint8_t* piece_bytes;
-};
-
-// Stop sequences of a decode forward (stopseq.hip; cain_plan_forward_st / cain_plan_capture_st): the match runs after
-// the sampler, and after JSON mode's advance where that is on too (a token it took back is not consumed).
-struct CainStop {
-  const int* stop_on;          // per row: 0 off, else the row has stop strings
-  void* sstate;                // per row: 48 bytes of StopState (stop_match.h)
-  const int32_t* stop_len;     // [M][8]: bytes of each string, 0 for an unused entry
-  const uint8_t* stop_bytes;   // [M][8][32]
-  const int* piece_off;        // the piece table, as CainGrammar's
-  const uint8_t* piece_bytes;
 };
 
 }  // extern "C"
@@ -332,30 +286,6 @@ int forward_spec(const Plan& p, int R, const CainRows& r, const CainSpec& s, hip
   return 0;
 }
 
-// What the _gr entries refuse before anything is launched: logprobs without logits; JSON mode on anything but a
-// decode forward (logits, sampler and the rows' sampling state), or with a table or state missing.
-bool gr_args_ok(const CainRows* r, int want_logits, int want_sample, const CainLogprob* lq, const CainGrammar* gr) {
-  if (!r || (lq && !want_logits)) return false;
-  if (lq && (!lq->topn || (want_sample && (!lq->keep || !lq->lp || !lq->top_id || !lq->top_lp)))) return false;
-  if (!gr) return true;
-  if (!want_logits || !want_sample || !r->n_gen || !r->done || !r->gen || r->ldg < 1) return false;
-  return gr->gram_on && gr->gstate && gr->piece_off && gr->piece_bytes;
-}
-
-// What the _st entries refuse on top of that: stop sequences on anything but a decode forward (logits, sampler and
-// the rows' sampling state), or with a table or state missing.
-bool st_args_ok(const CainRows* r, int want_logits, int want_sample, const CainStop* sq) {
-  if (!sq) return true;
-  if (!r || !want_logits || !want_sample || !r->n_gen || !r->done || !r->gen || r->ldg < 1) return false;
-  return sq->stop_on && sq->sstate && sq->stop_len && sq->stop_bytes && sq->piece_off && sq->piece_bytes;
-}
-
-bool spec_rows_ok(const Plan& p, int R, const CainRows* r, const CainSpec* s) {
-  if (!r || !s || R < 1 || s->K < 1 || s->K > SPEC_K_MAX) return false;
-  if (!r->n_gen || !r->max_new || !r->done || !r->hist || !r->gen || !r->sample_params) return false;
-  return R * (s->K + 1) <= max_rows(p.d) && s->vocab <= p.d.V;
-}
-
 // One speculative step whose drafts a draft model proposes (spec.h CainSpecDraft): the draft rows from the decode
 // state, the draft plan's forward over 2 R rows (each sequence's catch-up row and its own row, sampled with the
 // request's options), K - 1 further draft forwards over R rows, each fed by the token the one before sampled; every
@@ -379,20 +309,66 @@ int forward_spec_model(const Plan& p, const Plan& d2, const Plan& d1, int R, con
   return 0;
 }
 
-// What the _spec_model entries refuse before anything is launched: what spec_rows_ok refuses, a CainSpec that is not
-// in given mode over the draft record's own buffers, 2 R rows above what a forward of the draft plan may have, plans
-// of different T_max, a draft vocabulary beyond the draft plan's, a null buffer.
-bool spec_model_ok(const Plan& p, const Plan* d2, const Plan* d1, int R, const CainRows* r, const CainSpec* s,
-                   const CainSpecDraft* sd) {
-  if (!spec_rows_ok(p, R, r, s) || !d2 || !d1 || !sd) return false;
-  if (s->mode != 1 || sd->K != s->K || sd->given != s->given || sd->seq != s->seq || sd->ldv != s->ldv ||
-      sd->lds != s->lds || sd->slots != s->slots)
+// What both step entries refuse before anything is launched (`capture`: cain_step_capture, of `steps` steps).
+// First what can be told without reading the plan: a null record, plan or rows, a combination that does not exist,
+// a missing buffer.
+//   lp          logprobs without logits, or with a result buffer missing
+//   gr, st      JSON mode or stop sequences on anything but a decode forward (logits, sampler and the rows' sampling
+//               state), or with a table or state missing
+//   spec        together with lp, gr or st (the K + 1 expanded rows would each need the state after their drafts);
+//               K outside 1 .. SPEC_K_MAX; rows without sampling state; M (K + 1) rows above what a forward of the
+//               plan may have; a draft vocabulary beyond the plan's
+//   spec_draft  without spec, or a spec that is not in given mode over the draft record's own buffers; a draft plan
+//               or a buffer missing; 2 M rows above what a forward of the draft plan may have; plans of different
+//               T_max; a draft vocabulary beyond the draft plan's
+bool step_ok(const CainStep* sp, bool capture, int steps) {
+  if (!sp || !sp->plan || !sp->rows || (capture && steps < 1) || sp->M < 1) return false;
+  const CainStep& s = *sp;
+  const CainRows& r = *s.rows;
+  const CainSpec* sc = s.spec;
+  const CainSpecDraft* sd = s.spec_draft;
+  if ((capture || sc) && !(s.want_logits && s.want_sample)) return false;
+  if ((sc && (s.lp || s.gr || s.st)) || (sd && !sc)) return false;
+  if (s.lp && (!s.want_logits || !s.lp->topn)) return false;
+  if (s.lp && s.want_sample && (!s.lp->keep || !s.lp->lp || !s.lp->top_id || !s.lp->top_lp)) return false;
+  if ((s.gr || s.st) && (!s.want_logits || !s.want_sample || !r.n_gen || !r.done || !r.gen || r.ldg < 1)) return false;
+  if (s.gr && !(s.gr->gram_on && s.gr->gstate && s.gr->piece_off && s.gr->piece_bytes)) return false;
+  if (s.st && !(s.st->stop_on && s.st->sstate && s.st->stop_len && s.st->stop_bytes && s.st->piece_off &&
+                s.st->piece_bytes))
     return false;
-  if (d2->d.T_max != p.d.T_max || d1->d.T_max != p.d.T_max || d2->d.V != d1->d.V) return false;
-  if (2 * R > max_rows(d2->d) || R > max_rows(d1->d)) return false;
-  if (sd->dvocab < 1 || sd->dvocab > d2->d.V || sd->dbos < 0 || sd->dbos >= sd->dvocab || sd->ldg < 1) return false;
-  return sd->dvalid && sd->p0 && sd->nd && sd->r_tok && sd->r_pos && sd->r_slot && sd->r_n_gen && sd->r_max_new &&
-         sd->r_done && sd->r_hist && sd->r_gen && sd->r_params && r->tok && r->pos && r->slot;
+  if (sc && (sc->K < 1 || sc->K > SPEC_K_MAX || !r.n_gen || !r.max_new || !r.done || !r.hist || !r.gen ||
+             !r.sample_params))
+    return false;
+  if (sd) {
+    if (!s.draft2 || !s.draft1) return false;
+    if (sc->mode != 1 || sd->K != sc->K || sd->given != sc->given || sd->seq != sc->seq || sd->ldv != sc->ldv ||
+        sd->lds != sc->lds || sd->slots != sc->slots)
+      return false;
+    if (sd->dvocab < 1 || sd->dbos < 0 || sd->dbos >= sd->dvocab || sd->ldg < 1) return false;
+    if (!(sd->dvalid && sd->p0 && sd->nd && sd->r_tok && sd->r_pos && sd->r_slot && sd->r_n_gen && sd->r_max_new &&
+          sd->r_done && sd->r_hist && sd->r_gen && sd->r_params && r.tok && r.pos && r.slot))
+      return false;
+  }
+  // ... then against the plans
+  const CainPlanDesc& d = static_cast<const Plan*>(s.plan)->d;
+  if (s.M * (sc ? sc->K + 1 : 1) > max_rows(d) || (sc && sc->vocab > d.V)) return false;
+  if (sd) {
+    const CainPlanDesc& d2 = static_cast<const Plan*>(s.draft2)->d;
+    const CainPlanDesc& d1 = static_cast<const Plan*>(s.draft1)->d;
+    if (d2.T_max != d.T_max || d1.T_max != d.T_max || d2.V != d1.V) return false;
+    if (2 * s.M > max_rows(d2) || s.M > max_rows(d1) || sd->dvocab > d2.V) return false;
+  }
+  return true;
+}
+
+// The step of a record step_ok passed: the plain forward, or the speculative step with or without a draft model.
+int run_step(const CainStep& s, hipStream_t st) {
+  const Plan& p = *static_cast<const Plan*>(s.plan);
+  if (s.spec_draft)
+    return forward_spec_model(p, *static_cast<const Plan*>(s.draft2), *static_cast<const Plan*>(s.draft1), s.M,
+                              *s.rows, *s.spec, *s.spec_draft, st);
+  if (s.spec) return forward_spec(p, s.M, *s.rows, *s.spec, st);
+  return forward(p, s.M, *s.rows, s.want_logits, s.want_sample, st, s.lp, s.gr, s.st);
 }
 
 // `steps` calls of `step` recorded on `st` into one executable graph (null and *err on failure).
@@ -454,109 +430,23 @@ CAIN_API void cain_w4a8_set_min_rows(int m) { g_w4a8_min_rows = m > 16 ? m : 16;
 
 CAIN_API const char* cain_plan_last_failure() { return g_fail; }
 
-// The decode forward with stop sequences (CainStop), under JSON mode when `gr` is given and with token
-// log-probabilities when `lq` is: `gr` and `sq` need want_logits and want_sample (refused before any launch
-// otherwise); with all three null it runs what cain_plan_forward runs.
-CAIN_API int cain_plan_forward_st(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
-                                  const CainLogprob* lq, const CainGrammar* gr, const CainStop* sq, hipStream_t st) {
-  auto* p = static_cast<Plan*>(plan);
+// Enqueue one step on `st`: 0, -1 for what step_ok refuses (nothing launched), else the first failing launch's code
+// (cain_plan_last_failure names it).
+CAIN_API int cain_step_run(const CainStep* s, hipStream_t st) {
   g_fail[0] = 0;
-  if (M < 1 || M > max_rows(p->d) || !gr_args_ok(rows, want_logits, want_sample, lq, gr) ||
-      !st_args_ok(rows, want_logits, want_sample, sq))
-    return -1;
-  return forward(*p, M, *rows, want_logits, want_sample, st, lq, gr, sq);
+  if (!step_ok(s, false, 1)) return -1;
+  return run_step(*s, st);
 }
 
-CAIN_API int cain_plan_forward(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
-                               hipStream_t st) {
-  return cain_plan_forward_st(plan, M, rows, want_logits, want_sample, nullptr, nullptr, nullptr, st);
-}
-
-// The same forward with token log-probabilities (CainLogprob): needs want_logits; a null `lq` is cain_plan_forward.
-CAIN_API int cain_plan_forward_lp(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
-                                  const CainLogprob* lq, hipStream_t st) {
-  return cain_plan_forward_st(plan, M, rows, want_logits, want_sample, lq, nullptr, nullptr, st);
-}
-
-// The decode forward under JSON mode (CainGrammar): cain_plan_forward_st without stop sequences.
-CAIN_API int cain_plan_forward_gr(void* plan, int M, const CainRows* rows, int want_logits, int want_sample,
-                                  const CainLogprob* lq, const CainGrammar* gr, hipStream_t st) {
-  return cain_plan_forward_st(plan, M, rows, want_logits, want_sample, lq, gr, nullptr, st);
-}
-
-// Record `steps` decode steps over M rows into a graph; returns the executable graph (or null).  Each step with its
-// token log-probabilities when `lq` is given, under JSON mode when `gr` is and with stop sequences when `sq` is (all
-// null: the graph of cain_plan_capture, launch for launch).
-CAIN_API void* cain_plan_capture_st(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
-                                    const CainGrammar* gr, const CainStop* sq, hipStream_t st, int* err) {
-  auto* p = static_cast<Plan*>(plan);
+// Record `steps` such steps on `st` (one stream: no parallel branch) into a graph; returns the executable graph, or
+// null with *err set (-1 for what step_ok refuses).
+CAIN_API void* cain_step_capture(const CainStep* s, int steps, hipStream_t st, int* err) {
   *err = 0;
-  if (M < 1 || M > max_rows(p->d) || steps < 1 || !gr_args_ok(rows, 1, 1, lq, gr) || !st_args_ok(rows, 1, 1, sq)) {
+  if (!step_ok(s, true, steps)) {
     *err = -1;
     return nullptr;
   }
-  return capture_steps(st, steps, err, [&] { return forward(*p, M, *rows, 1, 1, st, lq, gr, sq); });
-}
-
-CAIN_API void* cain_plan_capture_gr(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
-                                    const CainGrammar* gr, hipStream_t st, int* err) {
-  return cain_plan_capture_st(plan, M, rows, steps, lq, gr, nullptr, st, err);
-}
-
-CAIN_API void* cain_plan_capture_lp(void* plan, int M, const CainRows* rows, int steps, const CainLogprob* lq,
-                                    hipStream_t st, int* err) {
-  return cain_plan_capture_gr(plan, M, rows, steps, lq, nullptr, st, err);
-}
-
-CAIN_API void* cain_plan_capture(void* plan, int M, const CainRows* rows, int steps, hipStream_t st, int* err) {
-  return cain_plan_capture_lp(plan, M, rows, steps, nullptr, st, err);
-}
-
-// Speculative decoding: one step (draft -> forward over R (K + 1) expanded rows -> accept) over the R sequences of
-// `rows`; -1 when R (K + 1) exceeds the rows a forward of this plan may have.
-CAIN_API int cain_plan_forward_spec(void* plan, int R, const CainRows* rows, const CainSpec* spec, hipStream_t st) {
-  auto* p = static_cast<Plan*>(plan);
-  g_fail[0] = 0;
-  if (!spec_rows_ok(*p, R, rows, spec)) return -1;
-  return forward_spec(*p, R, *rows, *spec, st);
-}
-
-// `steps` such steps in one graph.
-CAIN_API void* cain_plan_capture_spec(void* plan, int R, const CainRows* rows, const CainSpec* spec, int steps,
-                                      hipStream_t st, int* err) {
-  auto* p = static_cast<Plan*>(plan);
-  *err = 0;
-  if (!spec_rows_ok(*p, R, rows, spec) || steps < 1) {
-    *err = -1;
-    return nullptr;
-  }
-  return capture_steps(st, steps, err, [&] { return forward_spec(*p, R, *rows, *spec, st); });
-}
-
-// Speculative decoding with a draft model: one step (the draft plan's K forwards -> given-mode verify -> accept ->
-// dvalid) over the R sequences of `rows`; -1, with nothing launched, for what spec_model_ok refuses.
-CAIN_API int cain_plan_forward_spec_model(void* plan, void* draft2, void* draft1, int R, const CainRows* rows,
-                                          const CainSpec* spec, const CainSpecDraft* sd, hipStream_t st) {
-  auto* p = static_cast<Plan*>(plan);
-  auto *d2 = static_cast<Plan*>(draft2), *d1 = static_cast<Plan*>(draft1);
-  g_fail[0] = 0;
-  if (!p || !spec_model_ok(*p, d2, d1, R, rows, spec, sd)) return -1;
-  return forward_spec_model(*p, *d2, *d1, R, *rows, *spec, *sd, st);
-}
-
-// `steps` such steps in one graph (one stream: no parallel branch).
-CAIN_API void* cain_plan_capture_spec_model(void* plan, void* draft2, void* draft1, int R, const CainRows* rows,
-                                            const CainSpec* spec, const CainSpecDraft* sd, int steps, hipStream_t st,
-                                            int* err) {
-  auto* p = static_cast<Plan*>(plan);
-  auto *d2 = static_cast<Plan*>(draft2), *d1 = static_cast<Plan*>(draft1);
-  *err = 0;
-  if (!p || !spec_model_ok(*p, d2, d1, R, rows, spec, sd) || steps < 1) {
-    *err = -1;
-    return nullptr;
-  }
-  return capture_steps(st, steps, err,
-                       [&] { return forward_spec_model(*p, *d2, *d1, R, *rows, *spec, *sd, st); });
+  return capture_steps(st, steps, err, [&] { return run_step(*s, st); });
 }
 
 CAIN_API int cain_graph_launch(void* exec, hipStream_t st) {
@@ -614,6 +504,7 @@ CAIN_API void* cain_stream_create_cu_limited(int n_cu) {
 
 CAIN_API int cain_stream_destroy(void* st) { return hipStreamDestroy(static_cast<hipStream_t>(st)) == hipSuccess ? 0 : -1; }
 
+CAIN_API int cain_step_size() { return int(sizeof(CainStep)); }
 CAIN_API int cain_rows_size() { return int(sizeof(CainRows)); }
 CAIN_API int cain_logprob_size() { return int(sizeof(CainLogprob)); }
 CAIN_API int cain_grammar_size() { return int(sizeof(CainGrammar)); }

@@ -252,18 +252,20 @@ def test_entries_refuse_bad_arguments():
     eng = _engine("tiny-llama3.1:8b", "tiny-mistral:7b", K=1, max_batch=2, keep_natural=False,
                   draft_weight_dtype="q4_k")
     small = DecodeEngine("tiny-mistral:7b", device=DEV, max_batch=2, max_context=128, weight_dtype="q4_k")
-    lib = ops.load_spec_model()
-    plan, d2, d1, rs, s, sd = eng._spec_model_args(2)
+    lib = ops.load()
+    ok = eng._step(2, eng.rows, True, True, spec_mode=0)  # the engine's own record of a step over 2 sequences
+    plan, d2, d1 = ok.plan, ok.draft2, ok.draft1
+    rs, s, sd = ok.keep[0], ok.keep[4], ok.keep[5]
     stream = ctypes.c_void_p(eng.stream.cuda_stream)
     err = ctypes.c_int(0)
     bufs = eng._spec_draft_bufs()
     bufs["nd"].fill_(-7)
 
-    def both(plan, d2, d1, R, s, sd):
-        rc = lib.cain_plan_forward_spec_model(plan, d2, d1, R, ctypes.byref(rs), ctypes.byref(s), ctypes.byref(sd),
-                                              stream)
-        g = lib.cain_plan_capture_spec_model(plan, d2, d1, R, ctypes.byref(rs), ctypes.byref(s), ctypes.byref(sd), 1,
-                                             stream, ctypes.byref(err))
+    def both(plan, d2, d1, R, s, sd, rs=rs):
+        step = ops.CainStep(plan=plan, draft2=d2, draft1=d1, rows=ctypes.pointer(rs), spec=ctypes.pointer(s),
+                            spec_draft=ctypes.pointer(sd), M=R, want_logits=1, want_sample=1)
+        rc = lib.cain_step_run(ctypes.byref(step), stream)
+        g = lib.cain_step_capture(ctypes.byref(step), 1, stream, ctypes.byref(err))
         return rc, g, err.value
 
     bad = ops.spec_struct(eng._spec_bufs(), 1)
@@ -272,7 +274,7 @@ def test_entries_refuse_bad_arguments():
     bad_sd.K = 8
     assert both(plan, d2, d1, 2, bad, bad_sd) == (-1, None, -1)
     assert both(plan, d2, d1, 0, s, sd) == (-1, None, -1)
-    p128 = ctypes.c_void_p(small._plan(4))
+    p128 = small._plan(4)
     assert both(plan, p128, p128, 2, s, sd) == (-1, None, -1)  # plans of different T_max
     assert both(plan, d2, d1, 2, ops.spec_struct(eng._spec_bufs(), 0), sd) == (-1, None, -1)  # not given mode
     null = ops.spec_draft_struct(bufs)
@@ -283,11 +285,9 @@ def test_entries_refuse_bad_arguments():
     spec33 = ops.spec_alloc(40, 1, 2, T_MAX, wide.cfg.vocab, DEV)
     sd33 = ops.spec_draft_alloc(spec33, eng.draft.cfg.vocab, eng.draft.cfg.bos_id)
     rs_w = wide._rows_struct(wide.rows, True)
-    args = (ctypes.c_void_p(wide._plan(66)), d2, d1, 33, ctypes.byref(rs_w), ctypes.byref(ops.spec_struct(spec33, 1)),
-            ctypes.byref(ops.spec_draft_struct(sd33)))
     assert eng.draft.weight_dtype == "q4_k" and eng.draft.row_cap == 64
-    assert lib.cain_plan_forward_spec_model(*args, stream) == -1
-    assert lib.cain_plan_capture_spec_model(*args, 1, stream, ctypes.byref(err)) is None and err.value == -1
+    assert both(wide._plan(66), d2, d1, 33, ops.spec_struct(spec33, 1), ops.spec_draft_struct(sd33), rs_w) == \
+        (-1, None, -1)
     torch.cuda.synchronize()
     assert bufs["nd"].cpu().tolist() == [-7] * eng.max_batch  # nothing was launched
     # ... and the same arguments unchanged are accepted (the engine's own call)

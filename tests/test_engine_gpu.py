@@ -235,3 +235,43 @@ def test_cu_limited_engine_matches_full_device(name, dtype, cus):
     assert ops.cu_budget() == full
     a.close()
     b.close()
+
+
+def test_feature_subsets_graph_equals_eager_and_graph_keys():
+    """Every subset of {logprobs, JSON mode, stop string} on one engine: the graph replay and the eager steps give the
+    same tokens (and bit-identical logprobs), and the replay caches exactly the two graphs of that subset, under the
+    key ``(rows, steps)`` followed by the subset's tags in the order lp, gr, st; eager steps cache none.  The stop
+    string never occurs, so no row ends on it."""
+    import itertools
+
+    import numpy as np
+
+    from jsonmode_vocab import json_test_vocabulary
+
+    eng = DecodeEngine("tiny-llama3.1:8b", device="cuda", max_batch=2, max_context=256, seed=5, steps_per_graph=4)
+    eng.set_json_vocab(json_test_vocabulary())
+    bits = lambda xs: np.asarray(xs, dtype=np.float32).view(np.uint32).tolist()  # noqa: E731
+    for lp, gr, st in itertools.product((False, True), repeat=3):  # the subset without a feature first
+        opts = [dict(temperature=0.8, seed=21 + i, eos_id=-1, **(dict(stop="\x00never") if st else {}))
+                for i in range(2)]
+        kw = dict(logprobs=lp, top_logprobs=3 if lp else 0, format="json" if gr else None)
+        before = set(eng._graphs)
+        a = eng.generate(PROMPTS[:2], 12, opts, use_graph=True, **kw)
+        tags = tuple(t for t, on in (("lp", lp), ("gr", gr), ("st", st)) if on)
+        assert set(eng._graphs) - before == {(2, 4) + tags, (2, 1) + tags}, (tags, set(eng._graphs) - before)
+        cached = set(eng._graphs)
+        b = eng.generate(PROMPTS[:2], 12, opts, use_graph=False, **kw)
+        assert set(eng._graphs) == cached
+        assert [r.tokens for r in a] == [r.tokens for r in b], tags
+        assert all(r.stop_hit is None for r in a + b)
+        if not gr:
+            assert all(r.eval_count == 12 for r in a), tags
+        if lp:
+            for x, y in zip(a, b):
+                assert bits(x.logprobs) == bits(y.logprobs) and len(x.logprobs) == x.eval_count, tags
+                assert [[i for i, _ in t] for t in x.top_logprobs] == [[i for i, _ in t] for t in y.top_logprobs]
+                assert [bits([v for _, v in t]) for t in x.top_logprobs] == \
+                    [bits([v for _, v in t]) for t in y.top_logprobs], tags
+        if not (lp or gr or st):
+            assert eng._lp is None and eng._gr is None and eng._st is None
+    eng.close()

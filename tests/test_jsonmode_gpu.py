@@ -125,7 +125,7 @@ def test_mask_refusals():
     lg = torch.zeros(1, 1024, device=DEV)
     z = torch.zeros(1, dtype=torch.int32, device=DEV)
     st = ops.json_states([jm.INITIAL], DEV)
-    lib = ops.load_grammar()
+    lib = ops.load()
     args = lambda V, ldl, cm=None: (ops._p(lg), ldl, V, 1, ops._p(z), ops._p(z), ops._p(st), ops._p(table["piece_off"]),  # noqa: E731
                                     ops._p(table["piece_bytes"]), cm, None)
     assert lib.cain_json_mask(*args((1 << 23) + 16, (1 << 23) + 16)) != 0  # ids must fit the mantissa

@@ -9,18 +9,22 @@ def test_kernel_library_loads_and_binds():
     lib = ops.load()
     for sym in ("cain_gemm_bf16", "cain_gemm_size", "cain_gemm_fp8", "cain_gemm_mxfp4", "cain_gemm_gguf", "cain_gemm_fp8a8",
                 "cain_gemm_mxfp4a8", "cain_gemm_ws_bytes", "cain_rmsnorm", "cain_embed", "cain_attention", "cain_sample",
-                "cain_plan_create", "cain_plan_forward", "cain_plan_capture", "cain_graph_launch",
+                "cain_plan_create", "cain_step_run", "cain_step_capture", "cain_graph_launch",
                 "cain_graph_destroy", "cain_sample_params_size", "cain_rows_size", "cain_plan_desc_size"):
         assert hasattr(lib, sym), sym
 
 
 def test_struct_layouts_match_native():
-    from cain_amd.engine.engine import _CainLayer, _CainPlanDesc, _CainRows
-
     lib = ops.load()
-    assert lib.cain_plan_desc_size() == ctypes.sizeof(_CainPlanDesc)
-    assert lib.cain_rows_size() == ctypes.sizeof(_CainRows)
-    assert lib.cain_layer_size() == ctypes.sizeof(_CainLayer)
+    assert lib.cain_plan_desc_size() == ctypes.sizeof(ops.CainPlanDesc)
+    assert lib.cain_rows_size() == ctypes.sizeof(ops.CainRows)
+    assert lib.cain_layer_size() == ctypes.sizeof(ops.CainLayer)
+    assert lib.cain_logprob_size() == ctypes.sizeof(ops.CainLogprob)
+    assert lib.cain_grammar_size() == ctypes.sizeof(ops.CainGrammar)
+    assert lib.cain_stop_size() == ctypes.sizeof(ops.CainStop)
+    assert lib.cain_spec_size() == ctypes.sizeof(ops.CainSpec)
+    assert lib.cain_spec_draft_size() == ctypes.sizeof(ops.CainSpecDraft)
+    assert lib.cain_step_size() == ctypes.sizeof(ops.CainStep)
     assert lib.cain_sample_params_size() == ops.SAMPLE_BYTES == 48
     assert lib.cain_gemm_size() == ctypes.sizeof(ops.CainGemm)
 

@@ -98,7 +98,7 @@ def test_draft_kernel_matches_the_rule(K, R, mode):
 
 def test_draft_and_accept_refuse_bad_arguments():
     spec = ops.spec_alloc(2, 3, 2, T_MAX, V, DEV)
-    lib = ops.load_spec()
+    lib = ops.load()
     s = ops.spec_struct(spec, 0)
     s.K = 8
     import ctypes
@@ -422,10 +422,11 @@ def test_row_limit():
     assert eng.max_batch == 64 // 8 and eng.continuous().capacity == 8
     import ctypes
 
-    lib = ops.load_spec()
+    lib = ops.load()
     rs, s = eng._rows_struct(eng.rows, True), ops.spec_struct(eng._spec_bufs(), 0)
-    rc = lib.cain_plan_forward_spec(ctypes.c_void_p(eng._plan(64)), 9, ctypes.byref(rs), ctypes.byref(s),
-                                    ctypes.c_void_p(eng.stream.cuda_stream))
+    step = ops.CainStep(plan=eng._plan(64), rows=ctypes.pointer(rs), spec=ctypes.pointer(s), M=9, want_logits=1,
+                        want_sample=1)
+    rc = lib.cain_step_run(ctypes.byref(step), ctypes.c_void_p(eng.stream.cuda_stream))
     assert rc == -1  # 9 x 8 rows are more than a forward of this plan may have; nothing launched
     eng.close()
 

@@ -124,7 +124,7 @@ def test_kernel_against_the_python_rule_step_by_step(M):
 
 
 def test_entry_refusals():
-    lib = ops.load_stop()
+    lib = ops.load()
     table = ops.json_table([b"", b"a"], DEV)
     z = torch.zeros(64, dtype=torch.int32, device=DEV)
     st = ops.stop_states([ss.INITIAL], DEV)
