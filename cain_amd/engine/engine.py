@@ -130,10 +130,43 @@ class GenResult:
         return d
 
 
+#: the further sampling options (csrc/sample.hip SampleExt), each neutral at 0: ``min_p`` in [0, 1]; the presence and
+#: frequency penalties >= 0 (the few-row samplers' thresholds rest on penalties that only lower a logit)
+SAMPLE_EXT_DEFAULTS = dict(min_p=0.0, presence_penalty=0.0, frequency_penalty=0.0)
+SPEC_EXT_REFUSAL = ("min_p, presence_penalty and frequency_penalty cannot be combined with speculative decoding (the "
+                    "K + 1 expanded rows would each need their own record)")
+
+
+def ext_options(opts: Optional[Dict]) -> Dict:
+    """``min_p`` / ``presence_penalty`` / ``frequency_penalty`` of a request's options (None or absent: 0), as
+    floats; ValueError on a non-number, a non-finite value, ``min_p`` outside [0, 1] or a negative penalty."""
+    out = {}
+    for k, d in SAMPLE_EXT_DEFAULTS.items():
+        v = opts.get(k) if opts else None
+        if v is None:
+            v = d
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{k} must be a number, got {v!r}")
+        v = float(v)
+        if not math.isfinite(v):
+            raise ValueError(f"{k} must be finite, got {v!r}")
+        if k == "min_p" and not 0.0 <= v <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1], got {v!r}")
+        if k != "min_p" and v < 0.0:
+            raise ValueError(f"{k} must be >= 0, got {v!r}")
+        out[k] = v
+    return out
+
+
+def ext_active(o: Dict) -> bool:
+    return any(o.get(k, 0.0) != 0.0 for k in SAMPLE_EXT_DEFAULTS)
+
+
 def _row_options(opts: Optional[Dict], cfg: ModelConfig, index: int, base_seed: int) -> Dict:
     o = dict(OLLAMA_DEFAULTS)
     if opts:
         o.update({k: v for k, v in opts.items() if v is not None and k in OLLAMA_DEFAULTS})
+    ext = ext_options(opts)
     seed = o.get("seed")
     if seed is None:
         seed = (base_seed * 1000003 + index * 7919 + time.monotonic_ns()) & 0xFFFFFFFFFFFF
@@ -147,7 +180,7 @@ def _row_options(opts: Optional[Dict], cfg: ModelConfig, index: int, base_seed: 
                                             () if opts and "eos_id" in opts else cfg.stop_ids))[:3],
                 # stop strings (options.stop, engine/stopseq.py) under a name of their own: ``stop`` above is the ids
                 stop_strs=stopseq.parse_stop(opts.get("stop")) if opts else (),
-                seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
+                seed=int(seed) & 0xFFFFFFFFFFFFFFFF, **ext)
 
 
 def _stopped(toks: List[int], o: Dict) -> bool:
@@ -590,6 +623,9 @@ class DecodeEngine:
         self.sample_params = ops.sample_params_tensor(
             [dict(temperature=0.0, top_p=1.0, repeat_penalty=1.0, top_k=1, repeat_last_n=0, eos_id=-1, seed=0)] * R,
             dev)
+        # the rows' further options (ops.sample_ext_tensor), beside sample_params: the captured graphs hold this
+        # buffer's pointer, a request changes its contents
+        self.sample_ext = ops.sample_ext_tensor([{}] * R, dev)
         if self.weight_dtype in Q4_DTYPES:
             self._check_gguf_shapes(packed)
         self._layers = (ops.CainLayer * L)()
@@ -704,6 +740,7 @@ class DecodeEngine:
             r.n_gen, r.max_new, r.done = _ptr(rows["n_gen"]), _ptr(rows["max_new"]), _ptr(rows["done"])
             r.hist, r.gen, r.ldg = _ptr(rows["hist"]), _ptr(self.gen), self.gen.stride(0)
             r.sample_params = _ptr(self.sample_params)
+            r.sample_ext = _ptr(self.sample_ext)
         return r
 
     def _lp_bufs(self) -> Dict[str, torch.Tensor]:
@@ -1071,6 +1108,8 @@ class DecodeEngine:
         row_opts = [_row_options(o, self.cfg, i, self.seed) for i, o in enumerate(opts)]
         if self.speculative and any(o["stop_strs"] for o in row_opts):
             raise ValueError(SPEC_STOP_REFUSAL)
+        if self.speculative and any(ext_active(o) for o in row_opts):
+            raise ValueError(SPEC_EXT_REFUSAL)
         for i in range(B):
             budget = self.T_max - len(ids[i])
             if budget < 1:
@@ -1153,6 +1192,7 @@ class DecodeEngine:
             r["done"][:B].zero_()
             r["max_new"][:B].copy_(torch.tensor(nps, dtype=torch.int32))
             self.sample_params[: ops.SAMPLE_BYTES * B].copy_(ops.sample_params_tensor(row_opts, "cpu").to(dev))
+            self.sample_ext[: ops.SAMPLE_EXT_BYTES * B].copy_(ops.sample_ext_tensor(row_opts, "cpu").to(dev))
             lq = None
             if with_lp:
                 self._lp_bufs()["topn"][:B].copy_(torch.tensor(want, dtype=torch.int32))
@@ -1468,17 +1508,27 @@ def sample_host_candidates(logits: torch.Tensor, history: List[int], o: Dict):
     """What the samplers of csrc/sample.hip draw from, computed on the host: ``(ids, probs, cut)`` -- the top-k
     candidate ids after the repeat penalty (value descending, index ascending; the penalty in float32, each distinct
     recent id inside the vocabulary once), their probabilities at the temperature (float64, normalised over the
-    candidates) and the number of leading candidates the top-p cut keeps (the smallest prefix whose cumulative
-    probability is >= top_p).  Greedy (temperature <= 0): the argmax alone, the lowest index on ties."""
+    candidates) and the number of leading candidates the cut keeps (the shorter of the top-p prefix -- the smallest
+    whose cumulative probability is >= top_p -- and the ``min_p`` prefix).  The penalty stage follows sample.hip's
+    header: the repeat penalty, then ``v - fmaf(count, frequency_penalty, presence_penalty)`` with the id's count in
+    the window; the three further keys may be absent (neutral).  Greedy (temperature <= 0): the argmax alone, the
+    lowest index on ties; ``min_p`` is ignored."""
     lg = logits.detach().to(torch.float32).cpu().numpy().copy()
     V = lg.shape[0]
     rp = np.float32(o["repeat_penalty"])
-    if rp != np.float32(1.0) and o["repeat_last_n"] > 0:
+    pp, fp = np.float32(o.get("presence_penalty", 0.0)), np.float32(o.get("frequency_penalty", 0.0))
+    ext = pp != np.float32(0.0) or fp != np.float32(0.0)
+    if (rp != np.float32(1.0) or ext) and o["repeat_last_n"] > 0:
         n = min(int(o["repeat_last_n"]), SAMPLE_HIST, len(history))
-        for t in set(history[len(history) - n:]):
+        window = history[len(history) - n:]
+        for t in set(window):
             if 0 <= t < V:
                 v = lg[t]
-                lg[t] = v / rp if v > 0 else v * rp
+                if rp != np.float32(1.0):
+                    v = np.float32(v / rp) if v > 0 else np.float32(v * rp)
+                if ext:  # v - fmaf(count, frequency, presence): the product and sum rounded once, then the difference
+                    v = np.float32(v - np.float32(np.float64(window.count(t)) * np.float64(fp) + np.float64(pp)))
+                lg[t] = v
     if o["temperature"] <= 0:
         return np.array([int(np.argmax(lg))]), np.ones(1), 1
     k = o["top_k"] if 0 < o["top_k"] <= SAMPLE_TOPK_MAX else SAMPLE_TOPK_MAX
@@ -1492,6 +1542,9 @@ def sample_host_candidates(logits: torch.Tensor, history: List[int], o: Dict):
     top_p = np.float64(np.float32(o["top_p"]))
     if 0 < top_p < 1:
         cut = min(int(np.searchsorted(np.cumsum(p), top_p, side="left")) + 1, len(ids))
+    min_p = np.float64(np.float32(o.get("min_p", 0.0)))
+    if min_p > 0:  # the prefix with exp((v_i - v_0) / T) >= min_p (p[i] / p[0]: the same ratio), candidate 0 always
+        cut = min(cut, max(1, int(np.count_nonzero(p / p[0] >= min_p))))
     return ids, p, cut
 
 
@@ -1594,6 +1647,8 @@ class ContinuousBatch:
         stops = [o["stop_strs"] for o in row_opts]
         if eng.speculative and any(stops):
             raise ValueError(SPEC_STOP_REFUSAL)
+        if eng.speculative and any(ext_active(o) for o in row_opts):
+            raise ValueError(SPEC_EXT_REFUSAL)
         if eng.prefix_cache:
             self._trim_idled()
             plan = plan_prefix_reuse(eng.slot_tokens, self.free_slots, self.row_slot, ids, PREFIX_COPY_MIN)
@@ -1626,6 +1681,8 @@ class ContinuousBatch:
             r["done"][sl].zero_()
             r["max_new"][sl].copy_(torch.tensor(nps, dtype=torch.int32))
             eng.sample_params[ops.SAMPLE_BYTES * self.n: ops.SAMPLE_BYTES * (self.n + k)].copy_(ops.sample_params_tensor(row_opts, "cpu").to(eng.device))
+            eng.sample_ext[ops.SAMPLE_EXT_BYTES * self.n: ops.SAMPLE_EXT_BYTES * (self.n + k)].copy_(
+                ops.sample_ext_tensor(row_opts, "cpu").to(eng.device))
             if eng._lp is not None or any(w >= 0 for w in want):
                 eng._lp_bufs()["topn"][sl].copy_(torch.tensor(want, dtype=torch.int32))
             if eng.speculative:
@@ -1759,6 +1816,8 @@ class ContinuousBatch:
                 eng.gen[dst] = eng.gen[src]
                 sp = eng.sample_params.view(-1, ops.SAMPLE_BYTES)
                 sp[dst] = sp[src]
+                sx = eng.sample_ext.view(-1, ops.SAMPLE_EXT_BYTES)
+                sx[dst] = sx[src]
                 if eng._lp is not None:
                     for key in ("topn", "lp", "top_id", "top_lp"):
                         eng._lp[key][dst] = eng._lp[key][src]

@@ -94,7 +94,7 @@ class CainPlanDesc(ctypes.Structure):
 
 class CainRows(ctypes.Structure):
     _fields_ = ([(n, vp) for n in ("tok", "pos", "slot", "n_gen", "max_new", "done", "hist", "gen")]
-                + [("ldg", ci), ("sample_params", vp)])
+                + [("ldg", ci), ("sample_params", vp), ("sample_ext", vp)])
 
 
 class CainLogprob(ctypes.Structure):
@@ -172,7 +172,8 @@ def load() -> ctypes.CDLL:
         sizes = [(rec.__name__, entry, ctypes.sizeof(rec)) for rec, entry in _RECORD_SIZES] + [
             ("JSON_STATE_BYTES", "cain_json_state_size", JSON_STATE_BYTES),
             ("STOP_STATE_BYTES", "cain_stop_state_size", STOP_STATE_BYTES), ("STOP_MAX", "cain_stop_max", STOP_MAX),
-            ("STOP_LEN_MAX", "cain_stop_len_max", STOP_LEN_MAX)]
+            ("STOP_LEN_MAX", "cain_stop_len_max", STOP_LEN_MAX),
+            ("SAMPLE_EXT_BYTES", "cain_sample_ext_size", SAMPLE_EXT_BYTES)]
         for name, entry, mine in sizes:
             if hasattr(real, entry) and int(getattr(real, entry)()) != mine:
                 raise NativeOpsUnavailable(f"{LIB_PATH}: {name} is {int(getattr(real, entry)())}, this package's is "
@@ -216,15 +217,16 @@ def load() -> ctypes.CDLL:
                                           + [vp])
         lib.cain_attention_set_ring.argtypes = [ci]
         lib.cain_attention_set_body.argtypes = [ci]
-        lib.cain_sample.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]
-        lib.cain_sample_cm.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]
-        lib.cain_sample_lean.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp]
+        # (params, ext, stream: the last three of each; ext may be null)
+        lib.cain_sample.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp]
+        lib.cain_sample_cm.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp]
+        lib.cain_sample_lean.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp]
         lib.cain_gemm_set_cmax.argtypes = [vp]
         lib.cain_gemm_set_cmax.restype = None
         lib.cain_gemm_cmax_take.argtypes = []
         lib.cain_sample_set_cm.argtypes = [ci]
         lib.cain_gemm_set_skinny_split.argtypes = [ci]
-        lib.cain_sample_ex.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp,
+        lib.cain_sample_ex.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, vp, vp, vp,
                                        ctypes.c_longlong, vp]
         lib.cain_sample_set_trace.argtypes = [vp]
         lib.cain_sample_ws_bytes.restype = ctypes.c_longlong
@@ -916,34 +918,52 @@ def sample_params_tensor(rows, device) -> torch.Tensor:
     return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
 
 
+SAMPLE_EXT_DTYPE = [("min_p", "f4"), ("presence_penalty", "f4"), ("frequency_penalty", "f4"), ("reserved", "i4")]
+SAMPLE_EXT_BYTES = 16  # sizeof(SampleExt), csrc/sample.hip (cain_sample_ext_size)
+
+
+def sample_ext_tensor(rows, device) -> torch.Tensor:
+    """Pack the further per-row sampling options (list of dicts: ``min_p``, ``presence_penalty``,
+    ``frequency_penalty``; a missing key is neutral, 0) into the kernels' 16-byte SampleExt array."""
+    import numpy as np
+
+    arr = np.zeros(len(rows), dtype=np.dtype(SAMPLE_EXT_DTYPE, align=True))
+    for i, r in enumerate(rows):
+        for k in ("min_p", "presence_penalty", "frequency_penalty"):
+            arr[i][k] = r.get(k, 0.0)
+    assert arr.dtype.itemsize == SAMPLE_EXT_BYTES
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+
+
 def sample(logits, tok, pos, gen, n_gen, max_new, done, hist, slot, params, T_max, split: bool = False,
-           cmax=None, lean: bool = False) -> None:
+           cmax=None, lean: bool = False, ext=None) -> None:
     """On-device sampling + decode-state update (csrc/sample.hip).  ``split``: the two-stage kernel (vocabulary
     slices on 16 workgroups per row, last-arriver merge) that decode forwards of <= 64 rows use; ``cmax`` ([M][V/16]
     fp32 maxima of the logits' 16-column chunks, as the few-row LM head writes them): the chunk-maximum kernel that
     single-stream decode uses (``lean``: the lean chunk-maximum kernel); otherwise the one-workgroup-per-row
-    kernel."""
+    kernel.  ``ext``: the rows' SampleExt records (``sample_ext_tensor``); None is neutral."""
     lib = load()
     M, V = logits.shape[0], logits.shape[1]
     if cmax is not None and lean:
         _check(lib.cain_sample_lean(_p(logits), logits.stride(0), V, _p(cmax), _p(tok), _p(pos), _p(gen),
                                     gen.stride(0), _p(n_gen), _p(max_new), _p(done), _p(hist), _p(slot), T_max, M,
-                                    _p(params), _stream()), "sample_lean")
+                                    _p(params), _p(ext), _stream()), "sample_lean")
         return
     if cmax is not None:
         _check(lib.cain_sample_cm(_p(logits), logits.stride(0), V, _p(cmax), _p(tok), _p(pos), _p(gen), gen.stride(0),
                                   _p(n_gen), _p(max_new), _p(done), _p(hist), _p(slot), T_max, M, _p(params),
-                                  _stream()), "sample_cm")
+                                  _p(ext), _stream()), "sample_cm")
         return
     if split:
         nb = int(lib.cain_sample_ws_bytes(M))
         ws = _sample_ws(logits.device, nb)
         _check(lib.cain_sample_ex(_p(logits), logits.stride(0), V, _p(tok), _p(pos), _p(gen), gen.stride(0),
-                                  _p(n_gen), _p(max_new), _p(done), _p(hist), _p(slot), T_max, M, _p(params), _p(ws),
-                                  nb, _stream()), "sample")
+                                  _p(n_gen), _p(max_new), _p(done), _p(hist), _p(slot), T_max, M, _p(params), _p(ext),
+                                  _p(ws), nb, _stream()), "sample")
         return
     _check(lib.cain_sample(_p(logits), logits.stride(0), V, _p(tok), _p(pos), _p(gen), gen.stride(0), _p(n_gen),
-                           _p(max_new), _p(done), _p(hist), _p(slot), T_max, M, _p(params), _stream()), "sample")
+                           _p(max_new), _p(done), _p(hist), _p(slot), T_max, M, _p(params), _p(ext), _stream()),
+           "sample")
 
 
 LOGPROB_TOP_MAX = 20  # top_logprobs limit: entries per token in the top-n buffers (csrc/logprob.hip LP_TOP)

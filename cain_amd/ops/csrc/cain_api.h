@@ -61,6 +61,7 @@ struct CainRows {
   int* gen;
   int ldg;
   const void* sample_params;
+  const void* sample_ext;  // [M] SampleExt (sample.hip: min_p, presence and frequency penalties); null: neutral
 };
 
 // Token log-probabilities of a forward (logprob.hip; CainStep::lp).  Decode forwards (want_sample): the statistics
@@ -160,19 +161,20 @@ CAIN_API int cain_attention(const void* q, const void* kc, const void* vtc, cons
                             int Hkv, int hd, int T_max, int nsplit, float scale, hipStream_t st);
 CAIN_API int cain_sample(float* logits, int ldl, int V, int* tok, int* pos, int* gen, int ldg, int* n_gen,
                          const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                         const void* params, hipStream_t st);
+                         const void* params, const void* ext, hipStream_t st);
+CAIN_API int cain_sample_ext_size();
 CAIN_API long long cain_sample_ws_bytes(int M);
 CAIN_API int cain_sample_split_max();
 CAIN_API int cain_sample_cm_enabled();
 CAIN_API int cain_sample_cm(float* logits, int ldl, int V, const float* cmax, int* tok, int* pos, int* gen, int ldg,
                             int* n_gen, const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                            const void* params, hipStream_t st);
+                            const void* params, const void* ext, hipStream_t st);
 CAIN_API int cain_sample_lean(float* logits, int ldl, int V, const float* cmax, int* tok, int* pos, int* gen, int ldg,
                               int* n_gen, const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                              const void* params, hipStream_t st);
+                              const void* params, const void* ext, hipStream_t st);
 CAIN_API int cain_sample_ex(float* logits, int ldl, int V, int* tok, int* pos, int* gen, int ldg, int* n_gen,
                             const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                            const void* params, void* ws, long long ws_bytes, hipStream_t st);
+                            const void* params, const void* ext, void* ws, long long ws_bytes, hipStream_t st);
 CAIN_API int cain_logprob_rows(const float* logits, int ldl, int V, int M, const int* slot, const int* done,
                                const int* topn, int nmax, const int* target, float* lse, float* lp, int* top_id,
                                float* top_lp, hipStream_t st);

@@ -254,13 +254,15 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
     const int cm_mode = cain_sample_cm_enabled();
     const int e = !cm ? -1
                   : cm_mode == 3 ? cain_sample_lean(d.logits, d.V, d.V, p.cmax, r.tok, r.pos, r.gen, r.ldg, r.n_gen,
-                                                    r.max_new, r.done, r.hist, r.slot, d.T_max, M, r.sample_params, st)
+                                                    r.max_new, r.done, r.hist, r.slot, d.T_max, M, r.sample_params,
+                                                    r.sample_ext, st)
                                  : cain_sample_cm(d.logits, d.V, d.V, p.cmax, r.tok, r.pos, r.gen, r.ldg, r.n_gen,
-                                                  r.max_new, r.done, r.hist, r.slot, d.T_max, M, r.sample_params, st);
+                                                  r.max_new, r.done, r.hist, r.slot, d.T_max, M, r.sample_params,
+                                                  r.sample_ext, st);
     if (e > 0) CK(e);
     if (e < 0)
       CK(cain_sample_ex(d.logits, d.V, d.V, r.tok, r.pos, r.gen, r.ldg, r.n_gen, r.max_new, r.done, r.hist, r.slot,
-                        d.T_max, M, r.sample_params, p.sample_ws, p.sample_ws_bytes, st));
+                        d.T_max, M, r.sample_params, r.sample_ext, p.sample_ws, p.sample_ws_bytes, st));
     if (lq) CK(cain_logprob_chosen(d.logits, d.V, d.V, M, r.gen, r.ldg, lq->keep, lq->lp, st));
     if (gr)
       CK(cain_json_advance(M, d.V, gr->gram_on, r.gen, r.ldg, r.n_gen, r.done, gr->gstate, gr->piece_off,
@@ -277,7 +279,7 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
 int forward_spec(const Plan& p, int R, const CainRows& r, const CainSpec& s, hipStream_t st) {
   const int T = p.d.T_max;
   CK(cain_spec_draft(&s, R, T, r.tok, r.pos, r.slot, r.n_gen, r.max_new, r.done, r.hist, r.sample_params, st));
-  CainRows x{};
+  CainRows x{};  // (sample_ext stays null: the expanded rows have no SampleExt records, the engine refuses the mix)
   x.tok = s.x_tok, x.pos = s.x_pos, x.slot = s.x_slot, x.n_gen = s.x_n_gen, x.max_new = s.x_max_new;
   x.done = s.x_done, x.hist = s.x_hist, x.gen = s.x_gen, x.ldg = s.ldg, x.sample_params = s.x_params;
   CK(forward(p, R * (s.K + 1), x, 1, 1, st));
@@ -295,7 +297,7 @@ int forward_spec_model(const Plan& p, const Plan& d2, const Plan& d1, int R, con
                        const CainSpecDraft& sd, hipStream_t st) {
   const int T = p.d.T_max;
   CK(cain_spec_model_rows(&sd, R, T, r.tok, r.pos, r.slot, r.n_gen, r.max_new, r.done, r.hist, r.sample_params, st));
-  CainRows x{};
+  CainRows x{};  // (sample_ext null, as forward_spec's rows)
   x.tok = sd.r_tok, x.pos = sd.r_pos, x.slot = sd.r_slot, x.n_gen = sd.r_n_gen, x.max_new = sd.r_max_new;
   x.done = sd.r_done, x.hist = sd.r_hist, x.gen = sd.r_gen, x.ldg = sd.ldg, x.sample_params = sd.r_params;
   CK(forward(d2, 2 * R, x, 1, 1, st));

@@ -15,6 +15,23 @@
 //   pos[m]  += 1                 (position of that token)
 //   gen[m][n_gen[m]++] <- id     (output buffer, read back once at the end)
 //   hist ring of the last 64 ids (repeat penalty), done[m] on EOS / budget.
+//
+// Further per-row options travel in a second record, SampleExt (16 bytes; a null pointer or an all-zero record is
+// neutral and gives the tokens of a launch without it, bit for bit):
+//   * Penalty stage: active when repeat_last_n > 0, at least one token has been generated and repeat_penalty != 1 or
+//     presence_penalty != 0 or frequency_penalty != 0.  Its window is the repeat penalty's: the last
+//     min(repeat_last_n, 64, n_gen) ids of the row's ring, ids outside [0, V) ignored.  For each distinct id t of the
+//     window, c its number of occurrences in the window: first, only if repeat_penalty != 1, v = v > 0 ? v / rp :
+//     v * rp; then, only if one of the two is non-zero, v = v - fmaf(float(c), frequency_penalty, presence_penalty)
+//     (llama.cpp's rule, logit -= count * freq + (count > 0) * presence, counted inside the last-n window; an
+//     explicit fmaf, so the contraction setting cannot change the rounding).  presence_penalty and frequency_penalty
+//     are >= 0 (the host refuses others): the two-stage and lean kernels' thresholds rest on penalties that lower.
+//     A logit JSON mode masked (about -1e30) stays masked: a few units are below half an ulp of a float of that size.
+//   * min_p in [0, 1], 0 off: after top-k, candidate i (value descending, index ascending) is kept when
+//     exp((v_i - v_0) / T) >= min_p, the temperature-scaled term top-p sums; candidate 0 always.  The kept set is a
+//     prefix and the ratio does not change under renormalisation, so the final cut is the shorter of the top-p and
+//     min_p prefixes; renormalisation and the pick run over that cut.  Greedy (temperature <= 0) ignores min_p; the
+//     penalties still apply before the argmax.
 #include <cstdlib>
 
 #include "common.h"
@@ -29,6 +46,30 @@ struct SampleParams {
   int stop[3];  // further stop ids (a chat model's turn ends: <|eot_id|>, <|end|>, <end_of_turn>, ...); -1 unused
   uint64_t seed;
 };
+
+struct SampleExt {  // beside SampleParams (whose 48 bytes are pinned); all zero: neutral
+  float min_p;
+  float presence_penalty;
+  float frequency_penalty;
+  int reserved;
+};
+
+__device__ __forceinline__ SampleExt load_ext(const SampleExt* __restrict__ ext, int m) {
+  return ext ? ext[m] : SampleExt{0.f, 0.f, 0.f, 0};
+}
+__device__ __forceinline__ bool ext_pen(const SampleExt& X) {
+  return X.presence_penalty != 0.f || X.frequency_penalty != 0.f;
+}
+// The penalty window of a row with ng generated tokens (0: the penalty stage is off).
+__device__ __forceinline__ int pen_window(const SampleParams& P, const SampleExt& X, int ng) {
+  return ((P.repeat_penalty != 1.0f || ext_pen(X)) && P.repeat_last_n > 0) ? min(min(P.repeat_last_n, 64), ng) : 0;
+}
+// The penalised value of a logit whose id occurs c >= 1 times in the window.
+__device__ __forceinline__ float penalised(float v, int c, const SampleParams& P, const SampleExt& X) {
+  if (P.repeat_penalty != 1.0f) v = v > 0.f ? v / P.repeat_penalty : v * P.repeat_penalty;
+  if (ext_pen(X)) v = v - fmaf(float(c), X.frequency_penalty, X.presence_penalty);
+  return v;
+}
 
 __device__ __forceinline__ uint32_t ord_u32(float f) {
   uint32_t u = __float_as_uint(f);
@@ -74,7 +115,7 @@ __device__ __forceinline__ float lane63(float v) {
 }
 __device__ __forceinline__ float wave_total(float v) { return lane63(wave_incl_scan(v)); }
 
-__device__ int draw_topk_wave(const float* sv, const int* si, int n, const SampleParams& P, int ng) {
+__device__ int draw_topk_wave(const float* sv, const int* si, int n, const SampleParams& P, int ng, float min_p) {
   const int lane = threadIdx.x & 63;
   const float invT = 1.0f / P.temperature;
   const float mx = sv[0] * invT;
@@ -92,6 +133,17 @@ __device__ int draw_topk_wave(const float* sv, const int* si, int n, const Sampl
       const unsigned long long hit = __ballot(i < n && c >= P.top_p);
       if (hit) { cut = c0 + __ffsll((long long)hit); break; }
       carry = lane63(c);
+    }
+  }
+  // min_p: the prefix whose terms are >= min_p times candidate 0's (1 up to the rounding of mx; its equals tie with
+  // it exactly), never longer than the top-p cut.  min_p == 0: nothing here runs
+  if (min_p > 0.f) {
+    const float thr = min_p * __expf(sv[0] * invT - mx);
+    for (int c0 = 0; c0 < cut; c0 += 64) {
+      const int i = c0 + lane;
+      const float ei = __expf(sv[i < cut ? i : 0] * invT - mx);
+      const unsigned long long drop = __ballot(i > 0 && i < cut && ei < thr);
+      if (drop) { cut = c0 + __ffsll((long long)drop) - 1; break; }
     }
   }
   float zc = 0.f;
@@ -181,10 +233,11 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
     float* __restrict__ logits, int ldl, int V, int* __restrict__ tok, int* __restrict__ pos,
     int* __restrict__ gen, int ldg, int* __restrict__ n_gen, const int* __restrict__ max_new,
     int* __restrict__ done, int* __restrict__ hist, const int* __restrict__ slot, int T_max,
-    const SampleParams* __restrict__ params) {
+    const SampleParams* __restrict__ params, const SampleExt* __restrict__ ext) {
   const int m = blockIdx.x;
   if (slot[m] < 0 || done[m]) return;
   const SampleParams P = params[m];
+  const SampleExt X = load_ext(ext, m);
   float* lg = logits + (size_t)m * ldl;
   const int tid = threadIdx.x;
   __shared__ int s_hist[HIST];
@@ -200,10 +253,11 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
   __shared__ int red_i[SAMPLE_THREADS / 64];
   __shared__ int s_choice;
 
-  // ---- repeat penalty (llama.cpp semantics: once per distinct recent id), one lane per history slot
+  // ---- penalties (llama.cpp semantics: once per distinct recent id, with its count in the window), one lane per
+  // history slot: the lane of an id's newest occurrence counts the older ones
   const int* hr = hist + (size_t)m * HIST;
   const int ng = n_gen[m];
-  const int nrep = (P.repeat_penalty != 1.0f && P.repeat_last_n > 0) ? min(min(P.repeat_last_n, HIST), ng) : 0;
+  const int nrep = pen_window(P, X, ng);
   if (nrep > 0) {
     if (tid < HIST) s_hist[tid] = (tid < nrep) ? hr[(ng - 1 - tid) & (HIST - 1)] : -1;
     __syncthreads();
@@ -212,8 +266,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
       bool first = id >= 0 && id < V;
       for (int j = 0; j < tid; ++j) first &= (s_hist[j] != id);
       if (first) {
-        const float v = lg[id];
-        lg[id] = v > 0.f ? v / P.repeat_penalty : v * P.repeat_penalty;
+        int c = 1;
+        if (ext_pen(X))
+          for (int j = tid + 1; j < nrep; ++j) c += (s_hist[j] == id);
+        lg[id] = penalised(lg[id], c, P, X);
       }
     }
     __syncthreads();
@@ -352,7 +408,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_kernel(
     // ---- rank the candidates (value desc, index asc); keep the top K in sorted order
     const int nk = rank_candidates(cval, cidx, min(s_nc, MAXC), K, sv, si, SAMPLE_THREADS);
     if (tid < 64) {
-      const int pick = draw_topk_wave(sv, si, nk, P, ng);
+      const int pick = draw_topk_wave(sv, si, nk, P, ng, X.min_p);
       if (tid == 0) s_choice = pick;
     }
     __syncthreads();
@@ -505,10 +561,11 @@ __global__ __launch_bounds__(SS_THREADS) void sample_split_kernel(
     const float* __restrict__ logits, int ldl, int V, int* __restrict__ tok, int* __restrict__ pos,
     int* __restrict__ gen, int ldg, int* __restrict__ n_gen, const int* __restrict__ max_new,
     int* __restrict__ done, int* __restrict__ hist, const int* __restrict__ slot, int T_max,
-    const SampleParams* __restrict__ params, const SampleWs ws) {
+    const SampleParams* __restrict__ params, const SampleExt* __restrict__ ext, const SampleWs ws) {
   const int m = blockIdx.x, part = blockIdx.y;
   if (slot[m] < 0 || done[m]) return;  // the same for every workgroup of the row: no ticket is taken
   const SampleParams P = params[m];
+  const SampleExt X = load_ext(ext, m);
   const float* lg = logits + (size_t)m * ldl;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   ss_stamp(ws, 0);
@@ -555,12 +612,13 @@ __global__ __launch_bounds__(SS_THREADS) void sample_split_kernel(
   e[SS_NJ * 4] = ti < v1 ? lg[ti < V ? ti : tid] : -INFINITY;
   auto eid = [&](int k) { return k < SS_NJ * 4 ? v0 + 4 * (tid + (k >> 2) * SS_THREADS) + (k & 3) : ti; };
 
-  // ---- repeat penalty (llama.cpp semantics: each distinct recent id once), applied to the CANDIDATES: it only
-  // lowers values, so with R = #history ids, at least K of the top K + R raw elements keep their value and the
+  // ---- penalties (llama.cpp semantics: each distinct recent id once, with its count in the window), applied to
+  // the CANDIDATES: they only lower values (a repeat penalty >= 1; the presence and frequency penalties are >= 0 and
+  // are subtracted), so with R = #history ids, at least K of the top K + R raw elements keep their value and the
   // (K + R)-th largest raw thread maximum is a lower bound of the penalised K-th largest; gathering raw >= that
   // bound keeps every penalised top-K element.  The history ids go to LDS while the slice is in flight.
   const int ng = n_gen[m];
-  const int nrep = (P.repeat_penalty != 1.0f && P.repeat_last_n > 0) ? min(min(P.repeat_last_n, HIST), ng) : 0;
+  const int nrep = pen_window(P, X, ng);
   int rs = 0;  // history ids in this slice (with repeats: an upper bound of the distinct ones)
   if (tid < HIST) {
     const int id = tid < nrep ? hist[(size_t)m * HIST + ((ng - 1 - tid) & (HIST - 1))] : -1;
@@ -597,20 +655,18 @@ __global__ __launch_bounds__(SS_THREADS) void sample_split_kernel(
   ss_stamp(ws, 3);
   if (ws.trace && tid == 0) ws.trace[((size_t)m * SS_P + part) * 8 + 6] = (unsigned long long)s_nc;
   const int nc1 = min(s_nc, MAXC);
-  if (nrep > 0) {  // penalise the candidates whose id is in the history (16-byte LDS reads of the id list)
+  if (nrep > 0) {  // penalise the candidates whose id is in the history, by its count there (16-byte LDS reads of
+                   // the id list; slots past the window hold -1, no candidate's id)
     const i32x4* h4 = reinterpret_cast<const i32x4*>(s_hist);
     for (int a = tid; a < nc1; a += SS_THREADS) {
       const int id = cidx[a];
-      bool hit = false;
+      int c = 0;
 #pragma unroll
       for (int h = 0; h < HIST / 4; ++h) {
         const i32x4 hv = h4[h];
-        hit |= (hv[0] == id) | (hv[1] == id) | (hv[2] == id) | (hv[3] == id);
+        c += int(hv[0] == id) + int(hv[1] == id) + int(hv[2] == id) + int(hv[3] == id);
       }
-      if (hit) {
-        const float v = cval[a];
-        cval[a] = v > 0.f ? v / P.repeat_penalty : v * P.repeat_penalty;
-      }
+      if (c > 0) cval[a] = penalised(cval[a], c, P, X);
     }
     __syncthreads();
   }
@@ -690,19 +746,21 @@ __global__ __launch_bounds__(SS_THREADS) void sample_split_kernel(
   const int n = rank_candidates(cval, cidx, min(s_nc, MAXC), KL, sv, si, SS_THREADS);
   ss_stamp(ws, 6);
   if (tid < 64) {
-    const int choice = greedy ? si[0] : draw_topk_wave(sv, si, n, P, ng);
+    const int choice = greedy ? si[0] : draw_topk_wave(sv, si, n, P, ng, X.min_p);
     if (tid == 0) advance_row(m, choice, ng, P, tok, pos, gen, ldg, n_gen, max_new, done, hist, T_max);
   }
   ss_stamp(ws, 7);
 }
 
 // params: device array of M SampleParams (per-row options, so one captured graph
-// serves trials with different seeds / temperatures).
+// serves trials with different seeds / temperatures); ext: device array of M SampleExt, or null (neutral) -- the
+// same for every sampler entry below.
 CAIN_API int cain_sample(float* logits, int ldl, int V, int* tok, int* pos, int* gen, int ldg, int* n_gen,
                          const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                         const void* params, hipStream_t st) {
+                         const void* params, const void* ext, hipStream_t st) {
   hipLaunchKernelGGL(sample_kernel, dim3(M), dim3(SAMPLE_THREADS), 0, st, logits, ldl, V, tok, pos, gen, ldg, n_gen,
-                     max_new, done, hist, slot, T_max, reinterpret_cast<const SampleParams*>(params));
+                     max_new, done, hist, slot, T_max, reinterpret_cast<const SampleParams*>(params),
+                     reinterpret_cast<const SampleExt*>(ext));
   return int(hipGetLastError());
 }
 
@@ -725,10 +783,11 @@ CAIN_API void cain_sample_set_split_max(int rows) { g_split_max = rows; }
 // else the one-workgroup kernel.  ws must hold cain_sample_ws_bytes(M) zeroed bytes (null: one-workgroup kernel).
 CAIN_API int cain_sample_ex(float* logits, int ldl, int V, int* tok, int* pos, int* gen, int ldg, int* n_gen,
                             const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                            const void* params, void* ws, long long ws_bytes, hipStream_t st) {
+                            const void* params, const void* ext, void* ws, long long ws_bytes, hipStream_t st) {
   if (!ws || M > cain_sample_split_max() || ws_bytes < cain_sample_ws_bytes(M) || V < 4 * SS_P ||
       (V + SS_P - 1) / SS_P + 3 > SS_NJ * 4 * SS_THREADS)
-    return cain_sample(logits, ldl, V, tok, pos, gen, ldg, n_gen, max_new, done, hist, slot, T_max, M, params, st);
+    return cain_sample(logits, ldl, V, tok, pos, gen, ldg, n_gen, max_new, done, hist, slot, T_max, M, params, ext,
+                       st);
   SampleWs w{};
   char* p = static_cast<char*>(ws);
   w.ctr = reinterpret_cast<unsigned*>(p);  // first: the tickets
@@ -740,7 +799,8 @@ CAIN_API int cain_sample_ex(float* logits, int ldl, int V, int* tok, int* pos, i
   w.cn = reinterpret_cast<int*>(p);
   w.trace = g_sample_trace;
   hipLaunchKernelGGL(sample_split_kernel, dim3(M, SS_P), dim3(SS_THREADS), 0, st, logits, ldl, V, tok, pos, gen, ldg,
-                     n_gen, max_new, done, hist, slot, T_max, reinterpret_cast<const SampleParams*>(params), w);
+                     n_gen, max_new, done, hist, slot, T_max, reinterpret_cast<const SampleParams*>(params),
+                     reinterpret_cast<const SampleExt*>(ext), w);
   return int(hipGetLastError());
 }
 
@@ -768,10 +828,11 @@ __global__ __launch_bounds__(SS_THREADS) void sample_cm_kernel(
     float* __restrict__ logits, int ldl, int V, const float* __restrict__ cmax, int* __restrict__ tok,
     int* __restrict__ pos, int* __restrict__ gen, int ldg, int* __restrict__ n_gen, const int* __restrict__ max_new,
     int* __restrict__ done, int* __restrict__ hist, const int* __restrict__ slot, int T_max,
-    const SampleParams* __restrict__ params) {
+    const SampleParams* __restrict__ params, const SampleExt* __restrict__ ext) {
   const int m = blockIdx.x;
   if (slot[m] < 0 || done[m]) return;
   const SampleParams P = params[m];
+  const SampleExt X = load_ext(ext, m);
   float* lg = logits + (size_t)m * ldl;
   const int C = V >> 4;
   const float* cm = cmax + (size_t)m * C;
@@ -789,10 +850,10 @@ __global__ __launch_bounds__(SS_THREADS) void sample_cm_kernel(
   __shared__ int s_nc;
   __shared__ int s_choice;
 
-  // ---- 1. repeat penalty, in place
+  // ---- 1. penalties, in place (as sample_kernel)
   const int* hr = hist + (size_t)m * HIST;
   const int ng = n_gen[m];
-  const int nrep = (P.repeat_penalty != 1.0f && P.repeat_last_n > 0) ? min(min(P.repeat_last_n, HIST), ng) : 0;
+  const int nrep = pen_window(P, X, ng);
   if (tid < HIST) s_hist[tid] = (tid < nrep) ? hr[(ng - 1 - tid) & (HIST - 1)] : -1;
   __syncthreads();
   bool first = false;  // this thread's history id is the first occurrence of a valid id
@@ -801,8 +862,10 @@ __global__ __launch_bounds__(SS_THREADS) void sample_cm_kernel(
     first = id >= 0 && id < V;
     for (int j = 0; j < tid; ++j) first &= (s_hist[j] != id);
     if (first) {
-      const float v = lg[id];
-      lg[id] = v > 0.f ? v / P.repeat_penalty : v * P.repeat_penalty;
+      int c = 1;
+      if (ext_pen(X))
+        for (int j = tid + 1; j < nrep; ++j) c += (s_hist[j] == id);
+      lg[id] = penalised(lg[id], c, P, X);
     }
   }
   __syncthreads();
@@ -908,7 +971,7 @@ __global__ __launch_bounds__(SS_THREADS) void sample_cm_kernel(
   }
   const int nk = rank_candidates(cval, cidx, nc, K, sv, si, SS_THREADS);
   if (tid < 64) {
-    const int pick = (P.temperature <= 0.f) ? si[0] : draw_topk_wave(sv, si, nk, P, ng);
+    const int pick = (P.temperature <= 0.f) ? si[0] : draw_topk_wave(sv, si, nk, P, ng, X.min_p);
     if (tid == 0) s_choice = pick;
   }
   __syncthreads();
@@ -927,14 +990,16 @@ CAIN_API int cain_sample_cm_enabled() { return g_sample_cm; }
 CAIN_API void cain_sample_set_cm(int on) { g_sample_cm = on; }
 CAIN_API int cain_sample_cm(float* logits, int ldl, int V, const float* cmax, int* tok, int* pos, int* gen, int ldg,
                             int* n_gen, const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                            const void* params, hipStream_t st) {
+                            const void* params, const void* ext, hipStream_t st) {
   if (!cmax || V % 64 || V / 16 > CM_NJ * SS_THREADS) return -1;  // whole 16-byte chunk-max loads
   hipLaunchKernelGGL(sample_cm_kernel, dim3(M), dim3(SS_THREADS), 0, st, logits, ldl, V, cmax, tok, pos, gen, ldg,
-                     n_gen, max_new, done, hist, slot, T_max, reinterpret_cast<const SampleParams*>(params));
+                     n_gen, max_new, done, hist, slot, T_max, reinterpret_cast<const SampleParams*>(params),
+                     reinterpret_cast<const SampleExt*>(ext));
   return int(hipGetLastError());
 }
 
 CAIN_API int cain_sample_params_size() { return int(sizeof(SampleParams)); }
+CAIN_API int cain_sample_ext_size() { return int(sizeof(SampleExt)); }
 
 
 // =====================================================================================================
@@ -1134,7 +1199,8 @@ __global__ __launch_bounds__(LN_THREADS) void sample_lean_kernel(
     const float* __restrict__ logits, int ldl, int V, const float* __restrict__ cmax, int* __restrict__ tok,
     int* __restrict__ pos, int* __restrict__ gen, int ldg, int* __restrict__ n_gen, const int* __restrict__ max_new,
     int* __restrict__ done, int* __restrict__ hist, const int* __restrict__ slot, int T_max,
-    const SampleParams* __restrict__ params, unsigned long long* __restrict__ trace) {
+    const SampleParams* __restrict__ params, const SampleExt* __restrict__ ext,
+    unsigned long long* __restrict__ trace) {
   const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   auto stamp = [&](int i) {
     if (trace && tid == 0) trace[(size_t)m * 8 + i] = __builtin_amdgcn_s_memrealtime();
@@ -1150,6 +1216,7 @@ __global__ __launch_bounds__(LN_THREADS) void sample_lean_kernel(
   const int hslot = tid < HIST ? hist[(size_t)m * HIST + tid] : -1;
   const int sl = slot[m], dn = done[m], ng = n_gen[m];
   const SampleParams P = params[m];
+  const SampleExt X = load_ext(ext, m);
   if (sl < 0 || dn) return;
   const float* lg = logits + (size_t)m * ldl;
   extern __shared__ __attribute__((aligned(16))) float ln_smem[];
@@ -1164,8 +1231,9 @@ __global__ __launch_bounds__(LN_THREADS) void sample_lean_kernel(
   __shared__ __attribute__((aligned(16))) int cidx[MAXC + 4];
   __shared__ float s_tau, s_tv;
   __shared__ int s_ti, s_nc, s_choice;
+  __shared__ __attribute__((aligned(16))) int s_hid[HIST];  // the recent ids, for their counts (-1: none)
 
-  const int nrep = (P.repeat_penalty != 1.0f && P.repeat_last_n > 0) ? min(min(P.repeat_last_n, HIST), ng) : 0;
+  const int nrep = pen_window(P, X, ng);
   f32x4* s_cm4 = reinterpret_cast<f32x4*>(s_cm);
 #pragma unroll
   for (int j = 0; j < LN_NJ / 4; ++j)
@@ -1175,10 +1243,14 @@ __global__ __launch_bounds__(LN_THREADS) void sample_lean_kernel(
   if (hid >= V) hid = -1;
   float hv = 0.f;  // the recent id's logit (history lanes; needed in step 4 only)
   bool hfirst = false;
+  int hc = 1;  // occurrences of the history lane's id in the window (counted for a presence / frequency penalty)
   float cv[LN_NJ];  // this thread's chunk maxima; the bound sees the penalised chunks' as -inf
   float bv = -INFINITY;
   if (nrep > 0) {  // (uniform)
-    if (tid < HIST) hv = lg[hid >= 0 ? hid : 0];
+    if (tid < HIST) {
+      hv = lg[hid >= 0 ? hid : 0];
+      s_hid[tid] = hid;
+    }
     ln_u32x4* bm4 = reinterpret_cast<ln_u32x4*>(s_bm);
     const int nz4 = (bm_words + ((C + 127) >> 7 << 2)) >> 2;
     for (int w = tid; w < nz4; w += LN_THREADS) bm4[w] = ln_u32x4{0u, 0u, 0u, 0u};
@@ -1188,6 +1260,17 @@ __global__ __launch_bounds__(LN_THREADS) void sample_lean_kernel(
       hfirst = !(atomicOr(&s_bm[hid >> 5], bit) & bit);
       const int ch = hid >> 4;
       atomicOr(&s_cbm[ch >> 5], 1u << (ch & 31));
+    }
+    // the bitmap gives first-ness only: a distinct id's count is a compare against the 64 slots (wave 0 holds them
+    // all; 16-byte LDS reads, all independent).  Only with a presence / frequency penalty (uniform)
+    if (ext_pen(X) && hfirst) {
+      const i32x4* h4 = reinterpret_cast<const i32x4*>(s_hid);
+      hc = 0;
+#pragma unroll
+      for (int h = 0; h < HIST / 4; ++h) {
+        const i32x4 q = h4[h];
+        hc += int(q[0] == hid) + int(q[1] == hid) + int(q[2] == hid) + int(q[3] == hid);
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -1270,7 +1353,7 @@ __global__ __launch_bounds__(LN_THREADS) void sample_lean_kernel(
     for (int i = 0; i < 4; ++i) ev[4 * u + i] = qin && !((pen4 >> i) & 1u) ? lq[u][i] : -INFINITY;
   }
   // the last item: the distinct recent id's penalised logit (history lanes)
-  ev[NE - 1] = hfirst ? (hv > 0.f ? hv / P.repeat_penalty : hv * P.repeat_penalty) : -INFINITY;
+  ev[NE - 1] = hfirst ? penalised(hv, hc, P, X) : -INFINITY;
   auto eid = [&](int k) { return k < NE - 1 ? eb[k >> 2] + (k & 3) : hid; };  // (k constant after unrolling)
   stamp(4);
 
@@ -1298,7 +1381,7 @@ __global__ __launch_bounds__(LN_THREADS) void sample_lean_kernel(
   const int nk = ln_rank(cval, cidx, nc, K, sv, si);
   stamp(6);
   if (tid < 64) {
-    const int pick = nk == 0 ? 0 : (P.temperature <= 0.f ? si[0] : draw_topk_wave(sv, si, nk, P, ng));
+    const int pick = nk == 0 ? 0 : (P.temperature <= 0.f ? si[0] : draw_topk_wave(sv, si, nk, P, ng, X.min_p));
     if (lane == 0) s_choice = pick;
   }
   __syncthreads();
@@ -1316,7 +1399,7 @@ static size_t ln_lds_bytes(int V) {
 // loaded, elements gathered, ranked, end.
 CAIN_API int cain_sample_lean(float* logits, int ldl, int V, const float* cmax, int* tok, int* pos, int* gen, int ldg,
                               int* n_gen, const int* max_new, int* done, int* hist, const int* slot, int T_max, int M,
-                              const void* params, hipStream_t st) {
+                              const void* params, const void* ext, hipStream_t st) {
   if (!cmax || V % 64 || V / 16 > LN_C_MAX) return -1;
   static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_lean_kernel),
                                                hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1324,6 +1407,7 @@ CAIN_API int cain_sample_lean(float* logits, int ldl, int V, const float* cmax, 
   if (!attr) return -1;
   hipLaunchKernelGGL(sample_lean_kernel, dim3(M), dim3(LN_THREADS), ln_lds_bytes(V), st, logits, ldl, V, cmax, tok,
                      pos, gen, ldg, n_gen, max_new, done, hist, slot, T_max,
-                     reinterpret_cast<const SampleParams*>(params), g_sample_trace);
+                     reinterpret_cast<const SampleParams*>(params), reinterpret_cast<const SampleExt*>(ext),
+                     g_sample_trace);
   return int(hipGetLastError());
 }

@@ -193,6 +193,10 @@ class Backend:
         """Raise ValueError when this backend cannot serve ``options.stop`` for ``model`` (default: the option is
         accepted; a backend without a model ignores it, as it ignores the sampling options)."""
 
+    def check_sampling(self, model: str, ext: Dict[str, float]) -> None:
+        """Raise ValueError when this backend cannot serve the non-neutral ``min_p`` / ``presence_penalty`` /
+        ``frequency_penalty`` of ``ext`` for ``model`` (default: accepted, as the other sampling options are)."""
+
     def vocab_size(self, model: str) -> Optional[int]:
         """Token ids a request's ``context`` may hold are below this (None: not checked)."""
         return None
@@ -362,6 +366,11 @@ class EngineBackend(Backend):
     def check_stop(self, model: str, stops) -> None:
         if stops and self.speculative:
             raise ValueError("stop strings cannot be combined with speculative decoding (--speculative)")
+
+    def check_sampling(self, model: str, ext: Dict[str, float]) -> None:
+        if self.speculative:
+            raise ValueError("min_p, presence_penalty and frequency_penalty cannot be combined with speculative "
+                             "decoding (--speculative)")
 
     @staticmethod
     def _stream_decoder(eng, j: Job):
@@ -792,6 +801,17 @@ class OllamaHandler(BaseHTTPRequestHandler):
             try:
                 opts["stop"] = list(parse_stop(opts["stop"]))
                 self.scheduler.backend.check_stop(model, opts["stop"])
+            except ValueError as exc:
+                return self._send_json(400, {"error": str(exc)})
+        # min_p, presence_penalty, frequency_penalty: their ranges (README "Sampling options"), and what the backend
+        # cannot combine them with
+        if any(opts.get(k) is not None for k in ("min_p", "presence_penalty", "frequency_penalty")):
+            from ..engine.engine import ext_active, ext_options
+
+            try:
+                ext = ext_options(opts)
+                if ext_active(ext):
+                    self.scheduler.backend.check_sampling(model, ext)
             except ValueError as exc:
                 return self._send_json(400, {"error": str(exc)})
         n = opts.get("num_predict")
