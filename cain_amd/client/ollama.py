@@ -73,6 +73,22 @@ class GenerateResponse:
         return out
 
 
+@dataclass
+class EmbedResponse:
+    """The answer of ``POST /api/embed``: ``embeddings`` one vector per input, in order."""
+    data: Dict[str, Any]
+    wall_s: float
+    status: int = 200
+
+    @property
+    def embeddings(self) -> List[List[float]]:
+        return self.data.get("embeddings", [])
+
+    @property
+    def prompt_eval_count(self) -> int:
+        return int(self.data.get("prompt_eval_count", 0) or 0)
+
+
 class OllamaError(RuntimeError):
     pass
 
@@ -154,6 +170,27 @@ class OllamaClient:
         _lp_fields(body, logprobs, top_logprobs)
         return self._post_gen("/api/chat", body, stream, None)
 
+    def _post_json(self, path: str, body: Dict) -> Any:
+        c, r = self._request("POST", path, body)
+        try:
+            raw = r.read()
+            if r.status != 200:
+                raise OllamaError(f"POST {path}: HTTP {r.status}: {raw[:300]!r}")
+            return json.loads(raw)
+        finally:
+            c.close()
+
+    def embed(self, model: str, input, truncate: bool = True) -> EmbedResponse:
+        """``POST /api/embed``: ``input`` one text or a list of texts; ``truncate``: cut an input beyond the context
+        instead of refusing it (HTTP 400)."""
+        t0 = time.perf_counter()
+        data = self._post_json("/api/embed", {"model": model, "input": input, "truncate": bool(truncate)})
+        return EmbedResponse(data, time.perf_counter() - t0)
+
+    def embeddings(self, model: str, prompt: str) -> List[float]:
+        """``POST /api/embeddings``, the older form: one text, one vector."""
+        return self._post_json("/api/embeddings", {"model": model, "prompt": prompt})["embedding"]
+
     def _post_gen(self, path: str, body: Dict, stream: bool, on_chunk) -> GenerateResponse:
         t0 = time.perf_counter()
         c, r = self._request("POST", path, body)
@@ -213,13 +250,16 @@ def _iter_lines(resp) -> Iterator[str]:
 
 @dataclass
 class CurlRequest:
-    """``curl http://HOST:PORT/api/generate -d '{...}'`` as a watched child process."""
+    """``curl http://HOST:PORT/api/generate -d '{...}'`` as a watched child process; with ``input`` (a text or a list
+    of texts) the request is ``/api/embed``'s instead and ``wait()``'s ``data`` holds its ``embeddings``."""
     url: str
     model: str
-    prompt: str
+    prompt: str = ""
     stream: bool = False
     options: Optional[Dict] = None
     timeout_s: float = 600.0
+    input: Any = None
+    truncate: bool = True
     proc: Optional[subprocess.Popen] = None
     t_start: float = 0.0
     t_end: Optional[float] = None
@@ -229,15 +269,21 @@ class CurlRequest:
         curl = shutil.which("curl")
         if curl is None:
             raise OllamaError("curl not found (use OllamaClient instead)")
-        body: Dict[str, Any] = {"model": self.model, "prompt": self.prompt, "stream": self.stream}
-        if self.options:
-            body["options"] = self.options
-        base = self.url if "://" in self.url else f"http://{self.url}"
         self._out = tempfile.TemporaryFile()
         self.t_start = time.perf_counter()
-        self.proc = subprocess.Popen([curl, "-sS", "--max-time", str(self.timeout_s), f"{base}/api/generate",
-                                      "-d", json.dumps(body)], stdout=self._out, stderr=subprocess.PIPE)
+        self.proc = subprocess.Popen([curl] + self.arguments(), stdout=self._out, stderr=subprocess.PIPE)
         return self
+
+    def arguments(self) -> List[str]:
+        """curl's arguments for this request."""
+        base = self.url if "://" in self.url else f"http://{self.url}"
+        if self.input is not None:
+            path, body = "/api/embed", {"model": self.model, "input": self.input, "truncate": bool(self.truncate)}
+        else:
+            path, body = "/api/generate", {"model": self.model, "prompt": self.prompt, "stream": self.stream}
+        if self.options:
+            body["options"] = self.options
+        return ["-sS", "--max-time", str(self.timeout_s), f"{base}{path}", "-d", json.dumps(body)]
 
     @property
     def pid(self) -> int:
@@ -265,7 +311,7 @@ class CurlRequest:
         if "error" in objs[-1]:
             raise OllamaError(objs[-1]["error"])
         final = dict(objs[-1])
-        if self.stream:
+        if self.stream and self.input is None:
             final["response"] = "".join(o.get("response", "") for o in objs)
         return GenerateResponse(final, self.t_end - self.t_start, chunks=len(objs))
 

@@ -225,6 +225,18 @@ class ScoreResult:
         return -float(sum(self.logprobs))
 
 
+POOLINGS = ("last", "mean")
+
+
+@dataclass
+class EmbedResult:
+    """One prompt's embedding (``DecodeEngine.embed``): ``embedding`` d floats, ``prompt_eval_count`` the tokens that
+    went through the model, ``truncated`` whether the prompt was cut to the context."""
+    embedding: List[float]
+    prompt_eval_count: int
+    truncated: bool = False
+
+
 def logprob_host(logits: torch.Tensor, n: int = 0):
     """The definition on the host: float64 log-softmax of one row of fp32 logits; returns it ([V] float64 numpy) with
     the ``n`` most likely ``(id, logprob)`` pairs, logit descending and index ascending on ties (the samplers'
@@ -671,6 +683,7 @@ class DecodeEngine:
         d.flm_head = MFMT[packed["flm_head"]] if "flm_head" in packed else 0
         self._desc = d
         self._lp: Optional[Dict[str, torch.Tensor]] = None  # logprob buffers, allocated at first use (_lp_bufs)
+        self._pool: Optional[Dict[str, torch.Tensor]] = None  # embedding pooling buffers, likewise (_pool_bufs)
         self._spec: Optional[Dict] = None  # speculative buffers, allocated at first use (_spec_bufs)
         self._plans: Dict[int, int] = {}
         self._graphs: Dict[tuple, int] = {}
@@ -895,7 +908,7 @@ class DecodeEngine:
 
     def _step(self, M: int, rows, want_logits: bool, want_sample: bool, lp: Optional[ops.CainLogprob] = None,
               gr: Optional[ops.CainGrammar] = None, st: Optional[ops.CainStop] = None,
-              spec_mode: Optional[int] = None) -> ops.CainStep:
+              spec_mode: Optional[int] = None, pool: Optional[ops.CainPool] = None) -> ops.CainStep:
         """The call record of one step (csrc/cain_api.h CainStep): a forward over ``M`` rows with the given feature
         records, or -- ``spec_mode`` given (0: n-gram drafts, 1: the given drafts) -- a speculative step over ``M``
         sequences, whose drafts the draft model proposes where the engine has one.  The record points into the
@@ -909,15 +922,15 @@ class DecodeEngine:
             sp, sd = ops.spec_struct(self._spec_bufs(), 1), ops.spec_draft_struct(self._spec_draft_bufs())
         elif spec:
             sp = ops.spec_struct(self._spec_bufs(), spec_mode)
-        s.keep = (self._rows_struct(rows, bool(want_sample)), lp, gr, st, sp, sd)
-        for name, rec in zip(("rows", "lp", "gr", "st", "spec", "spec_draft"), s.keep):
+        s.keep = (self._rows_struct(rows, bool(want_sample)), lp, gr, st, sp, sd, pool)
+        for name, rec in zip(("rows", "lp", "gr", "st", "spec", "spec_draft", "pool"), s.keep):
             if rec is not None:
                 setattr(s, name, ctypes.pointer(rec))
         return s
 
     def _forward(self, M: int, rows, want_logits: bool, want_sample: bool, lp: Optional[ops.CainLogprob] = None,
-                 gr=None, st=None) -> None:
-        step = self._step(M, rows, want_logits, want_sample, lp, gr, st)
+                 gr=None, st=None, pool: Optional[ops.CainPool] = None) -> None:
+        step = self._step(M, rows, want_logits, want_sample, lp, gr, st, pool=pool)
         with self._cu_budget():
             ops.step_run(step, self._stream_h())
 
@@ -1332,26 +1345,113 @@ class DecodeEngine:
                 at += n
         return out
 
+    # ---------------------------------------------------------------- embeddings
+    def _pool_bufs(self) -> Dict[str, torch.Tensor]:
+        """Device buffers of embedding pooling (csrc/pool.hip), made at first use: the fp32 final gain -- the model's
+        own, unfolded, whatever the weight format -- the accumulators, counts and results per cache slot, and per
+        prefill row the RMSNorm scale and the run table."""
+        if self._pool is None:
+            dev, d, R = self.device, self.cfg.d_model, self.prefill_rows["tok"].shape[0]
+            z = lambda *s, dt=torch.float32: torch.zeros(*s, device=dev, dtype=dt)  # noqa: E731
+            self._pool = dict(gain=self._packed["final_gain"].to(dev).float().contiguous(), acc=z(self.max_batch, d),
+                              cnt=z(self.max_batch, dt=torch.int32), out=z(self.max_batch, d), rinv=z(R),
+                              seg_off=z(R + 1, dt=torch.int32), seg_dst=z(R, dt=torch.int32))
+        return self._pool
+
+    def _pool_struct(self, runs: int, mode: int) -> ops.CainPool:
+        b = self._pool_bufs()
+        return ops.CainPool(gain=_ptr(b["gain"]), seg_off=_ptr(b["seg_off"]), seg_dst=_ptr(b["seg_dst"]),
+                            acc=_ptr(b["acc"]), cnt=_ptr(b["cnt"]), rinv=_ptr(b["rinv"]), S=runs, mode=mode)
+
+    @torch.no_grad()
+    def embed(self, prompts: Sequence[Union[str, Sequence[int]]], pooling: str = "last", normalize: bool = True,
+              truncate: bool = True, slots: Optional[Sequence[int]] = None) -> List[EmbedResult]:
+        """Embeddings of prompts (ids or text, encoded as ``generate`` encodes them; an empty prompt embeds
+        ``[bos_id]``).  The hidden state of a prompt of n tokens is the residual stream after the last layer at each
+        position under the model's own final RMSNorm with its own gain (``weights.final_gain``: Gemma's 1 + w
+        included) -- what the LM head multiplies, before any fold.  ``pooling="last"``: the vector at position n - 1;
+        ``"mean"``: the fp32 sum over positions 0 .. n - 1 in ascending order, divided by n.  ``normalize``: the
+        pooled vector is L2-normalised.  ``truncate``: a prompt beyond the context keeps its first ``T_max`` tokens
+        (``truncated`` says so); without it such a prompt raises ValueError.
+        HIP backend: all n tokens go through prefill chunks, each carrying the pool record (csrc/pool.hip), then one
+        finishing launch and one copy of the vectors: no LM head, no sampler, no decode forward.  It writes cache slots
+        ``slots`` (default 0 .. B - 1 per pass of up to ``max_batch`` prompts), whose prefix-cache records die; on a
+        speculative engine the forward is a plain one and the draft cache is not written.  Torch backend: the
+        oracle's ``hidden``, pooled in fp32."""
+        if pooling not in POOLINGS:
+            raise ValueError(f"pooling must be one of {POOLINGS}, got {pooling!r}")
+        ids, cut = [], []
+        for p in prompts:
+            t = self.encode(p) or [self.cfg.bos_id]
+            if len(t) > self.T_max and not truncate:
+                raise ValueError(f"input of {len(t)} tokens exceeds the context ({self.T_max}) and truncate is off")
+            cut.append(len(t) > self.T_max)
+            ids.append(t[: self.T_max])
+        if self.backend == "torch":
+            vecs = []
+            for p in ids:
+                h = self.ref.hidden(torch.tensor([p], device=self.device))[0].float()
+                if pooling == "last":
+                    v = h[-1]
+                else:
+                    v = torch.zeros_like(h[0])
+                    for j in range(h.shape[0]):  # ascending position order, as the kernel
+                        v = v + h[j]
+                    v = v / float(h.shape[0])
+                if normalize:
+                    nrm = v.pow(2).sum().sqrt()
+                    v = v / nrm if float(nrm) > 0 else v
+                vecs.append(v.cpu().tolist())
+        else:
+            width = self.max_batch if slots is None else len(slots)
+            if width < 1:
+                raise ValueError("embed needs at least one cache slot")
+            mode = ops.POOL_MODES[pooling]
+            vecs = []
+            for i in range(0, len(ids), width):
+                group = ids[i:i + width]
+                use = list(range(len(group))) if slots is None else [int(s) for s in slots[:len(group)]]
+                self._forget_slots(use)
+                b = self._pool_bufs()
+                with torch.cuda.stream(self.stream):
+                    b["acc"].zero_()
+                    b["cnt"].zero_()
+                    if self._specd is not None:  # the draft cache no longer continues what these slots hold
+                        self._specd["dvalid"][torch.tensor(use, dtype=torch.long, device=self.device)] = 0
+                    self._prefill(group, use, pool_mode=mode)
+                    with self._cu_budget():
+                        rc = ops.pool_finish(b["acc"], b["cnt"], b["out"], normalize)
+                    if rc != 0:
+                        raise RuntimeError(f"cain_pool_finish failed (rc={rc})")
+                    out = b["out"][:len(group)].cpu()
+                    self.stream.synchronize()
+                vecs += out.tolist()
+        return [EmbedResult(v, len(p), c) for v, p, c in zip(vecs, ids, cut)]
+
     def _forget_slots(self, slots) -> None:
         """These slots are about to be written outside the continuous batch's bookkeeping: their records die."""
         for s in slots:
             self.slot_tokens[s] = []
 
     def _prefill(self, ids, slots: Optional[Sequence[int]] = None, start: Optional[Sequence[int]] = None,
-                 score_top: Optional[int] = None):
+                 score_top: Optional[int] = None, pool_mode: Optional[int] = None):
         """All prompt tokens but the last through the forward, into KV-cache slot ``slots[b]`` (default b).
+        ``pool_mode`` (``embed``; ops.POOL_*): the last token goes through too, and every chunk carries the pool
+        record -- its runs are the chunk's stretches of one prompt each, accumulated into row b of the pool buffers
+        (``last``: only the runs that end a prompt).
         ``start[b]``: row b's slot already holds positions ``< start[b]`` of this prompt; tokens
         ``ids[b][start[b]:-1]`` go in at positions ``start[b] ..`` (default: everything from 0).
         ``score_top`` (``score``): every chunk also runs the LM head and scores each row's next token on the device,
         with that many alternatives; returns the flat rows' (logprobs, top_logprobs)."""
-        flat_tok, flat_pos, flat_slot, flat_next = [], [], [], []
+        flat_tok, flat_pos, flat_slot, flat_next, flat_seq = [], [], [], [], []
         for b, p in enumerate(ids):
             j0 = 0 if start is None else int(start[b])
-            for j in range(j0, len(p) - 1):
+            for j in range(j0, len(p) - (pool_mode is None)):
                 flat_tok.append(p[j])
                 flat_pos.append(j)
                 flat_slot.append(b if slots is None else int(slots[b]))
-                flat_next.append(p[j + 1])
+                flat_next.append(p[j + 1] if j + 1 < len(p) else -1)
+                flat_seq.append(b)
         lps: List[float] = []
         tops: List[List[tuple]] = []
         self.prefill_rows_total += len(flat_tok)
@@ -1361,6 +1461,20 @@ class DecodeEngine:
             pr["tok"][:n].copy_(torch.tensor(flat_tok[c:c + n], dtype=torch.int32))
             pr["pos"][:n].copy_(torch.tensor(flat_pos[c:c + n], dtype=torch.int32))
             pr["slot"][:n].copy_(torch.tensor(flat_slot[c:c + n], dtype=torch.int32))
+            if pool_mode is not None:
+                # the chunk's runs: [c + off[s], c + off[s + 1]) are consecutive positions of prompt dst[s]
+                off = [0] + [j for j in range(1, n) if flat_seq[c + j] != flat_seq[c + j - 1]] + [n]
+                dst = [flat_seq[c + o] for o in off[:-1]]
+                # `last` takes only the runs that end their prompt: every run but the chunk's final one does
+                if pool_mode == ops.POOL_LAST and flat_pos[c + n - 1] != len(ids[dst[-1]]) - 1:
+                    off, dst = off[:-1], dst[:-1]
+                pb = self._pool_bufs()
+                if dst:
+                    pb["seg_off"][:len(off)].copy_(torch.tensor(off, dtype=torch.int32))
+                    pb["seg_dst"][:len(dst)].copy_(torch.tensor(dst, dtype=torch.int32))
+                self._forward(n, pr, want_logits=False, want_sample=False,
+                              pool=self._pool_struct(len(dst), pool_mode) if dst else None)
+                continue
             if score_top is None:
                 self._forward(n, pr, want_logits=False, want_sample=False)
                 continue
@@ -1708,6 +1822,17 @@ class ContinuousBatch:
             for s, rec in zip(slots, records):
                 eng.slot_tokens[s] = rec
         return rows
+
+    def embed(self, prompts: Sequence[Union[str, Sequence[int]]], pooling: str = "last", normalize: bool = True,
+              truncate: bool = True) -> List[EmbedResult]:
+        """``DecodeEngine.embed`` between graph chunks, on currently free cache slots only -- those with an empty
+        prefix-cache record first, then the shortest records -- in passes of as many prompts as there are free
+        slots.  The slots stay free (their records die); no live row's slot or decode state is touched."""
+        if not self.free_slots:
+            raise ValueError("no free slot to embed on")
+        eng = self.eng
+        order = sorted(self.free_slots, key=lambda s: len(eng.slot_tokens[s]))
+        return eng.embed(prompts, pooling=pooling, normalize=normalize, truncate=truncate, slots=order)
 
     def step(self, steps: Optional[int] = None) -> None:
         eng = self.eng

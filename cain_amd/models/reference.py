@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from .config import ModelConfig, rope_inv_freq
-from .weights import ModelWeights, effective_gain
+from .weights import ModelWeights, effective_gain, final_gain
 
 
 def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
@@ -164,6 +164,20 @@ class ReferenceModel:
             # bf16, but fp32 logits like the engine's LM head (fp32 accumulation, no bf16 rounding of the logits)
             return x.float() @ self.mw.lm_head.float().t()
         return (x @ self._w(self.mw.lm_head).t()).float()
+
+    @torch.no_grad()
+    def hidden(self, tokens: torch.Tensor, positions: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Tokens [B, T] -> the hidden states [B, T, d] (fp32) an embedding pools: the residual stream after the last
+        layer under the model's own final RMSNorm with its own gain (``weights.final_gain``: Gemma's 1 + w included,
+        and the true gain of a gain-folded copy, not its unit ``final_norm``) -- what the LM head multiplies, before
+        any fold; no LM head."""
+        B, T = tokens.shape
+        if positions is None:
+            positions = torch.arange(T, device=tokens.device).expand(B, T)
+        x = self.embed(tokens)
+        for li in range(self.cfg.n_layers):
+            x = self.layer(x, li, positions)
+        return rms_norm(x, final_gain(self.mw), self.cfg.norm_eps)
 
     @torch.no_grad()
     def greedy(self, prompt: torch.Tensor, n_new: int) -> torch.Tensor:

@@ -230,6 +230,10 @@ class ModelWeights:
     # weights kept in a file's quantised form (models/q4.py gguf_q4_native: GGUF Q4_0 / Q4_K blocks, Q6_K tensors
     # beside them), packed as stored by pack_for_engine when the engine's weight_dtype is that format
     native: Dict[str, object] = field(default_factory=dict)
+    # the model's own effective final RMSNorm gain, carried beside a copy whose ``final_norm`` is a unit gain because
+    # the gain was folded into ``lm_head`` (``_roundtrip``): what an embedding's hidden state is normed with
+    # (``final_gain``); None: ``final_norm`` is the model's own
+    final_gain: Optional[torch.Tensor] = None
 
     @property
     def device(self) -> torch.device:
@@ -271,6 +275,12 @@ def effective_gain(cfg: ModelConfig, w: torch.Tensor) -> torch.Tensor:
     return (w.float() + 1.0).to(w.dtype) if cfg.norm_add_one else w
 
 
+def final_gain(mw: "ModelWeights") -> torch.Tensor:
+    """The effective gain of the model's own final RMSNorm (Gemma's 1 + w included), also of a gain-folded copy:
+    the one gain of an embedding's hidden state, for the engine, the torch backend and the tests' reference."""
+    return mw.final_gain if mw.final_gain is not None else effective_gain(mw.cfg, mw.final_norm)
+
+
 def fold_gain(w: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     """W diag(g): the RMSNorm gain that feeds a GEMM folded into its weight columns (fp32 product, one
     bf16 rounding).  RMSNorm(x) W^T = inv(x) * (x (W diag(g))^T), so the fused kernels only need the
@@ -297,7 +307,7 @@ def _roundtrip(mw: ModelWeights, rt) -> ModelWeights:
                                    w_gate=rt(fold_gain(lw.w_gate, gm)), w_up=rt(fold_gain(lw.w_up, gm)),
                                    w_down=rt(lw.w_down)))
     lm = rt(fold_gain(mw.lm_head, effective_gain(cfg, mw.final_norm)))
-    return ModelWeights(cfg, mw.embed, _unit_gain(cfg, mw.final_norm), lm, layers)
+    return ModelWeights(cfg, mw.embed, _unit_gain(cfg, mw.final_norm), lm, layers, final_gain=final_gain(mw))
 
 
 def fp8_roundtrip_weights(mw: ModelWeights) -> ModelWeights:
@@ -340,7 +350,7 @@ def q4_roundtrip_weights(mw: ModelWeights, weight_dtype: str) -> ModelWeights:
                                    w_up=q4_roundtrip(fold_gain(lw.w_up, gm), f["wgu"]),
                                    w_down=q4_roundtrip(lw.w_down, f["w_down"])))
     lm = q4_roundtrip(fold_gain(mw.lm_head, effective_gain(cfg, mw.final_norm)), fm["lm_head"])
-    return ModelWeights(cfg, mw.embed, _unit_gain(cfg, mw.final_norm), lm, layers)
+    return ModelWeights(cfg, mw.embed, _unit_gain(cfg, mw.final_norm), lm, layers, final_gain=final_gain(mw))
 
 
 Q4_DTYPES = ("q4_0", "q4_k", "q4_k_m")
@@ -420,7 +430,8 @@ def pack_for_engine(mw: ModelWeights, free_natural: bool = False, weight_dtype: 
             lp.update(fqkv=fm.get("wqkv", fmt), fo=fm.get("wo", fmt), fgu=fm.get("wgu", fmt),
                       fdown=fm.get("w_down", fmt))
             layers.append(lp)
-        packed = {"layers": layers, "weight_dtype": weight_dtype, "q4_gain": True}
+        packed = {"layers": layers, "weight_dtype": weight_dtype, "q4_gain": True,
+                  "final_gain": final_gain(mw).float().contiguous()}
         packed["flm_head"] = native.get("lm_head_fmt", fmt)
         packed["lm_head"], packed["lm_head_scale"] = pack_native(native["lm_head"], packed["flm_head"],
                                                                  effective_gain(cfg, mw.final_norm).float())
@@ -466,7 +477,9 @@ def pack_for_engine(mw: ModelWeights, free_natural: bool = False, weight_dtype: 
         layers.append(lp)
         if free_natural:
             lw.wqkv = lw.wo = lw.w_gate = lw.w_up = lw.w_down = None
-    packed: Dict[str, object] = {"layers": layers, "weight_dtype": weight_dtype}
+    # the final gain unfolded, in fp32, beside the folded LM head: embeddings norm the hidden state with it (pool.hip)
+    packed: Dict[str, object] = {"layers": layers, "weight_dtype": weight_dtype,
+                                 "final_gain": final_gain(mw).float().contiguous()}
     lm = fold_gain(mw.lm_head, effective_gain(cfg, mw.final_norm))
     put(packed, "wlm_head", lm, mix["lm_head"] if mix else None)
     del lm

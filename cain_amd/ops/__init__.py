@@ -21,6 +21,8 @@ op                     source                      replaces (Ollama/llama.cpp)
 ``gemm_q6``            csrc/gemm_qstream.hip       the same on GGUF Q6_K blocks (a Q4_K_M file's 6-bit tensors), any M
 ``rmsnorm``            csrc/norm.hip               RMSNorm (standalone; the engine fuses it)
 ``embed``              csrc/norm.hip               embedding gather (+Gemma scale)
+``pool_rows``          csrc/pool.hip               embeddings: final RMSNorm + last / mean pooling of prefill rows
+``pool_finish``        csrc/pool.hip               embeddings: mean over the count, L2 normalisation
 ``attention``          csrc/attention.hip          decode / prefill attention (split-K, in-kernel combine)
 ``kv_copy_prefix``     csrc/kv_prefix.hip          a slot's cached prompt prefix copied to another slot
 ``sample``             csrc/sample.hip             repeat-penalty/temperature/top-k/top-p
@@ -126,13 +128,21 @@ class CainSpecDraft(ctypes.Structure):
     _fields_ = [(n, ci) for n in _SPECD_INTS] + [(n, vp) for n in _SPECD_PTRS]
 
 
+class CainPool(ctypes.Structure):
+    _fields_ = ([(n, vp) for n in ("gain", "seg_off", "seg_dst", "acc", "cnt", "rinv")] + [("S", ci), ("mode", ci)])
+
+
+POOL_MEAN, POOL_LAST = 0, 1  # CainPool.mode (csrc/cain_api.h)
+POOL_MODES = {"mean": POOL_MEAN, "last": POOL_LAST}
+
+
 class CainStep(ctypes.Structure):
     """The call record of ``cain_step_run`` / ``cain_step_capture`` (csrc/cain_api.h CainStep, which says what the
     entries refuse).  It holds raw pointers to the other records: whoever fills it keeps those objects alive."""
     _fields_ = ([("plan", vp), ("draft2", vp), ("draft1", vp), ("rows", ctypes.POINTER(CainRows)),
                  ("lp", ctypes.POINTER(CainLogprob)), ("gr", ctypes.POINTER(CainGrammar)),
                  ("st", ctypes.POINTER(CainStop)), ("spec", ctypes.POINTER(CainSpec)),
-                 ("spec_draft", ctypes.POINTER(CainSpecDraft))]
+                 ("spec_draft", ctypes.POINTER(CainSpecDraft)), ("pool", ctypes.POINTER(CainPool))]
                 + [(n, ci) for n in ("M", "want_logits", "want_sample")])
 
 
@@ -140,7 +150,7 @@ class CainStep(ctypes.Structure):
 _RECORD_SIZES = ((CainGemm, "cain_gemm_size"), (CainLayer, "cain_layer_size"), (CainPlanDesc, "cain_plan_desc_size"),
                  (CainRows, "cain_rows_size"), (CainLogprob, "cain_logprob_size"), (CainGrammar, "cain_grammar_size"),
                  (CainStop, "cain_stop_size"), (CainSpec, "cain_spec_size"), (CainSpecDraft, "cain_spec_draft_size"),
-                 (CainStep, "cain_step_size"))
+                 (CainPool, "cain_pool_size"), (CainStep, "cain_step_size"))
 
 _lib: Optional[ctypes.CDLL] = None
 _lock = threading.Lock()
@@ -212,6 +222,8 @@ def load() -> ctypes.CDLL:
         lib.cain_wgemm_plan.argtypes = [ci, ci, ci]
         lib.cain_rmsnorm.argtypes = [vp, ci, vp, vp, ci, ci, ci, cf, vp]
         lib.cain_embed.argtypes = [vp, vp, vp, ci, ci, ci, cf, vp]
+        lib.cain_pool_rows.argtypes = [vp, ci, ci, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, vp]
+        lib.cain_pool_finish.argtypes = [vp, vp, vp, ci, ci, ci, vp]
         lib.cain_attention.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, vp]
         lib.cain_attention_ex.argtypes = ([vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, cf, ci, cf, cf]
                                           + [vp])
@@ -722,6 +734,27 @@ def embed(tok: torch.Tensor, table: torch.Tensor, scale: float = 1.0, out=None) 
     out = torch.empty(M, d, device=table.device, dtype=table.dtype) if out is None else out
     _check(lib.cain_embed(_p(tok), _p(table), _p(out), out.stride(0), M, d, scale, _stream()), "embed")
     return out
+
+
+def pool_rows(x: torch.Tensor, gain: Optional[torch.Tensor], eps: float, seg_off: torch.Tensor, seg_dst: torch.Tensor,
+              mode: int, acc: torch.Tensor, cnt: torch.Tensor, rinv: torch.Tensor, d: Optional[int] = None) -> int:
+    """Embedding pooling of bf16 rows ``x [M, ldx]`` (csrc/pool.hip ``cain_pool_rows``): each run ``seg_off[s] ..
+    seg_off[s + 1]`` of rows goes, under RMSNorm with the fp32 ``gain``, into row ``seg_dst[s]`` of the fp32 ``acc
+    [B, d]`` and the int32 ``cnt [B]`` (``POOL_MEAN``: added in ascending row order; ``POOL_LAST``: the run's final
+    row written); ``rinv [M]`` receives the rows' RMSNorm scales.  Returns the entry's code: 0, or -1 for what it
+    refuses before any launch (``d`` not a multiple of 8 or above 16384, a null gain)."""
+    _gpu(x, gain, seg_off, seg_dst, acc, cnt, rinv)
+    d = x.shape[1] if d is None else d
+    return int(load().cain_pool_rows(_p(x), x.stride(0), x.shape[0], d, _p(gain), float(eps), _p(seg_off), _p(seg_dst),
+                                     seg_dst.numel(), int(mode), _p(acc), _p(cnt), _p(rinv), _stream()))
+
+
+def pool_finish(acc: torch.Tensor, cnt: torch.Tensor, out: torch.Tensor, normalize: bool = True) -> int:
+    """``out[b] = acc[b] / cnt[b]``, L2-normalised with ``normalize`` (csrc/pool.hip ``cain_pool_finish``); rows with
+    ``cnt[b] == 0`` are left untouched."""
+    _gpu(acc, cnt, out)
+    return int(load().cain_pool_finish(_p(acc), _p(cnt), _p(out), acc.shape[0], acc.shape[1], int(bool(normalize)),
+                                       _stream()))
 
 
 # ---------------------------------------------------------------- KV-cache layout (attention.hip header)

@@ -99,6 +99,22 @@ struct CainStop {
   const uint8_t* piece_bytes;
 };
 
+// Embedding pooling of a prefill-style forward (pool.hip; CainStep::pool): after the last layer the rows of `x` --
+// the residual stream -- go through the model's own final RMSNorm (the fp32 `gain`, never folded) into the fp32
+// accumulators of their sequences.  seg_off[S + 1] cuts the forward's rows into S runs of consecutive positions of
+// one sequence each, seg_dst[s] names the run's row of acc [B][d] / cnt [B]; the runs of one step name distinct rows.
+struct CainPool {
+  const float* gain;   // [d]
+  const int* seg_off;  // [S + 1], ascending, within 0 .. M
+  const int* seg_dst;  // [S]
+  float* acc;
+  int* cnt;
+  float* rinv;         // [M] scratch: each row's RMSNorm scale
+  int S;
+  int mode;            // POOL_MEAN: every row, in ascending order; POOL_LAST: each run's final row only
+};
+enum { POOL_MEAN = 0, POOL_LAST = 1 };
+
 // One step of a plan, the call record of cain_step_run (enqueue it once) and cain_step_capture (record `steps` of
 // them into one graph): a forward over M rows -- with `spec`, a speculative step over M sequences (spec.h).  A null
 // feature record leaves the launches exactly those of a step without the feature.  What runtime.hip step_ok refuses
@@ -113,6 +129,7 @@ struct CainStep {
   const CainStop* st;     // likewise
   const CainSpec* spec;   // draft -> forward over M (K + 1) expanded rows -> accept; not with lp / gr / st
   const CainSpecDraft* spec_draft;  // with `spec` in given mode: the draft model proposes the drafts
+  const CainPool* pool;   // after the last layer of a forward without logits or sampler; not with lp / gr / st / spec
   int M;
   int want_logits, want_sample;  // a speculative step and every captured step: both 1
 };
@@ -149,6 +166,12 @@ CAIN_API float* cain_gemm_cmax_claim(int N);
 // CUs the launch sizing of the persistent / CU-proportional grids assumes: the device's, or the smaller budget of
 // cain_set_cu_budget (runtime.hip) while the work runs on a CU-masked stream (cain_stream_create_cu_limited).
 CAIN_API int cain_cu_budget();
+
+// ---- embedding pooling (pool.hip)
+CAIN_API int cain_pool_rows(const void* x, int ldx, int M, int d, const float* gain, float eps, const int* seg_off,
+                            const int* seg_dst, int S, int mode, float* acc, int* cnt, float* rinv, hipStream_t st);
+CAIN_API int cain_pool_finish(const float* acc, const int* cnt, float* out, int B, int d, int normalize,
+                              hipStream_t st);
 
 // ---- the rest of a forward (norm.hip, attention.hip, sample.hip, logprob.hip, grammar.hip, stopseq.hip, spec.hip)
 CAIN_API int cain_embed(const int* tok, const void* E, void* out, int ldo, int M, int d, float scale, hipStream_t st);

@@ -149,8 +149,10 @@ int max_rows(const CainPlanDesc& d) {
 // lq: the caller's logprob buffers (null: none -- the launches are exactly those of a plan without the feature)
 // gr: JSON mode's buffers (null: none, likewise)
 // sq: the stop sequences' buffers (null: none, likewise)
+// pl: embedding pooling of the rows after the last layer (null: none, likewise; step_ok: no logits, no sampler)
 int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_sample, hipStream_t st,
-            const CainLogprob* lq = nullptr, const CainGrammar* gr = nullptr, const CainStop* sq = nullptr) {
+            const CainLogprob* lq = nullptr, const CainGrammar* gr = nullptr, const CainStop* sq = nullptr,
+            const CainPool* pl = nullptr) {
   const CainPlanDesc& d = p.d;
   const int qkv_dim = (d.H + 2 * d.Hkv) * d.hd;
   const int q_dim = d.H * d.hd;
@@ -229,6 +231,9 @@ int forward(const Plan& p, int M, const CainRows& r, int want_logits, int want_s
     CK(gemm(L.wdown, L.wdown8, L.sdown, d.act, d.ffn, d.ffn, d.d, d.x, d.d, nullptr, 0, nullptr, nullptr,
             /*EPI_RESID*/ 1, L.fdown));
   }
+  if (pl)
+    CK(cain_pool_rows(d.x, d.d, M, d.d, pl->gain, d.eps, pl->seg_off, pl->seg_dst, pl->S, pl->mode, pl->acc, pl->cnt,
+                      pl->rinv, st));
   if (want_logits) {
     // the LM head also writes the chunk maxima the chunk-max samplers start from (the bf16 skinny / wide kernels and
     // the few-row fp8 / MXFP4 / Q4 kernels; a kernel that does not leaves cain_gemm_cmax_take() at 0)
@@ -317,6 +322,8 @@ int forward_spec_model(const Plan& p, const Plan& d2, const Plan& d1, int R, con
 //   lp          logprobs without logits, or with a result buffer missing
 //   gr, st      JSON mode or stop sequences on anything but a decode forward (logits, sampler and the rows' sampling
 //               state), or with a table or state missing
+//   pool        together with logits, the sampler, lp, gr, st, spec or a capture; a buffer missing; more runs than
+//               rows; a width cain_pool_rows refuses
 //   spec        together with lp, gr or st (the K + 1 expanded rows would each need the state after their drafts);
 //               K outside 1 .. SPEC_K_MAX; rows without sampling state; M (K + 1) rows above what a forward of the
 //               plan may have; a draft vocabulary beyond the plan's
@@ -331,6 +338,12 @@ bool step_ok(const CainStep* sp, bool capture, int steps) {
   const CainSpecDraft* sd = s.spec_draft;
   if ((capture || sc) && !(s.want_logits && s.want_sample)) return false;
   if ((sc && (s.lp || s.gr || s.st)) || (sd && !sc)) return false;
+  if (s.pool) {
+    const CainPool& q = *s.pool;
+    if (capture || s.want_logits || s.want_sample || s.lp || s.gr || s.st || sc || sd) return false;
+    if (!(q.gain && q.seg_off && q.seg_dst && q.acc && q.cnt && q.rinv) || q.S < 0 || q.S > s.M) return false;
+    if (q.mode != POOL_MEAN && q.mode != POOL_LAST) return false;
+  }
   if (s.lp && (!s.want_logits || !s.lp->topn)) return false;
   if (s.lp && s.want_sample && (!s.lp->keep || !s.lp->lp || !s.lp->top_id || !s.lp->top_lp)) return false;
   if ((s.gr || s.st) && (!s.want_logits || !s.want_sample || !r.n_gen || !r.done || !r.gen || r.ldg < 1)) return false;
@@ -354,6 +367,7 @@ bool step_ok(const CainStep* sp, bool capture, int steps) {
   // ... then against the plans
   const CainPlanDesc& d = static_cast<const Plan*>(s.plan)->d;
   if (s.M * (sc ? sc->K + 1 : 1) > max_rows(d) || (sc && sc->vocab > d.V)) return false;
+  if (s.pool && (d.d % 8 || d.d < 8 || d.d > 16384)) return false;
   if (sd) {
     const CainPlanDesc& d2 = static_cast<const Plan*>(s.draft2)->d;
     const CainPlanDesc& d1 = static_cast<const Plan*>(s.draft1)->d;
@@ -370,7 +384,7 @@ int run_step(const CainStep& s, hipStream_t st) {
     return forward_spec_model(p, *static_cast<const Plan*>(s.draft2), *static_cast<const Plan*>(s.draft1), s.M,
                               *s.rows, *s.spec, *s.spec_draft, st);
   if (s.spec) return forward_spec(p, s.M, *s.rows, *s.spec, st);
-  return forward(p, s.M, *s.rows, s.want_logits, s.want_sample, st, s.lp, s.gr, s.st);
+  return forward(p, s.M, *s.rows, s.want_logits, s.want_sample, st, s.lp, s.gr, s.st, s.pool);
 }
 
 // `steps` calls of `step` recorded on `st` into one executable graph (null and *err on failure).

@@ -9,7 +9,7 @@ Commands: ``help``, ``config-create [dir]``, ``prepare`` (build the native
 libraries and HIP kernels in-tree), ``analyze <run_table.csv>`` (paper tables),
 ``serve`` (Ollama-compatible server on this host's GPU), ``generate``
 (one local generation, prints Ollama-style JSON), ``perplexity`` (a text's perplexity
-under a model, one JSON line).
+under a model, one JSON line), ``embed`` (embeddings of texts, one JSON line).
 
 Run options (new): ``--gpus N`` fans TODO rows out data-parallel over N GPU
 worker processes (``cain_amd.parallel``; ``--max-restarts`` relaunches after a
@@ -115,6 +115,13 @@ def cmd_perplexity(args: List[str]) -> None:
     perplexity.main(args)
 
 
+def cmd_embed(args: List[str]) -> None:
+    """Embeddings of texts under a model (``DecodeEngine.embed``; README "Embeddings"): one JSON line."""
+    from ..serve import server
+
+    server.embed_main(args)
+
+
 def cmd_convert(args: List[str]) -> None:
     """``convert <checkpoint dir | .gguf> <out.gguf> [--type F16]``: a checkpoint as a GGUF file with llama.cpp's
     conventions (models/gguf.py export_gguf), e.g. to run the same weights under llama.cpp / Ollama.  A Hugging Face
@@ -170,6 +177,7 @@ COMMANDS = {
     "generate": ("--model M --prompt P [--num-predict N] [--checkpoint PATH]", cmd_generate),
     "perplexity": ("--model TAG [--checkpoint PATH] [--weights W] [--kv K] (--file PATH | --prompt TEXT) [--ctx N] "
                    "[--batch B]", cmd_perplexity),
+    "embed": ("--model M [--weights W] (--input TEXT ... | --file F) [--pooling mean] [--no-normalize]", cmd_embed),
     "convert": ("<checkpoint dir | .gguf> <out.gguf> [--type F16|Q8_0|Q4_0|Q4_K|Q6_K|Q4_K_M|...]", cmd_convert),
     "help": ("", cmd_help),
 }

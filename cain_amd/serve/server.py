@@ -115,6 +115,30 @@ class Job:
     format: Optional[str] = None     # "json": Ollama's JSON mode (engine/jsonmode.py)
 
 
+@dataclass
+class EmbedJob:
+    """The scheduler's second job kind: the inputs of one ``/api/embed`` / ``/api/embeddings`` request, embedded raw
+    (no chat template) by the model's worker thread between decode chunks (``Backend.embed``)."""
+    model: str
+    inputs: List[str]
+    truncate: bool = True
+    done: threading.Event = field(default_factory=threading.Event)
+    result: Any = None               # List[EmbedResult]
+    error: Optional[BaseException] = None
+    t_submit: float = field(default_factory=time.perf_counter)
+
+
+EMBED_POOLINGS = ("last", "mean")
+
+
+def embed_pooling_setting(value: Optional[str] = None) -> str:
+    """The server's pooling mode: ``value`` (``serve --embed-pooling``), else ``CAIN_EMBED_POOLING``, else "last"."""
+    mode = value or os.environ.get("CAIN_EMBED_POOLING") or "last"
+    if mode not in EMBED_POOLINGS:
+        raise ValueError(f"embed pooling must be one of {EMBED_POOLINGS}, got {mode!r}")
+    return mode
+
+
 def logprob_entries(tok, ids, lps, tops) -> List[Dict[str, Any]]:
     """The response's ``logprobs`` entries of tokens ``ids`` with logprobs ``lps`` and alternatives ``tops``."""
     def one(i: int, lp: float) -> Dict[str, Any]:
@@ -182,6 +206,13 @@ class Backend:
     def max_batch(self, model: str) -> int:
         return 1
 
+    def embed(self, model: str, job: "EmbedJob", cb=None) -> None:
+        """Fill ``job.result`` with one ``EmbedResult`` per input (``cb``: the model's continuous batch, when the
+        worker runs one: the embedding then takes its free slots only)."""
+        raise NotImplementedError
+
+    embed_pooling = "last"  # the server's pooling mode (embed_pooling_setting)
+
     def model_info(self, model: str) -> Dict[str, Any]:
         return {}
 
@@ -238,8 +269,9 @@ class EngineBackend(Backend):
                  backend: Optional[str] = None, seed: int = 0, preload: bool = False, steps_per_graph: int = 8,
                  trace_dir: Optional[str] = None, weight_dtype: str = "bf16", continuous: bool = True,
                  kv_dtype: str = "bf16", prefix_cache: bool = False, speculative: int = 0,
-                 draft_model: Optional[str] = None):
+                 draft_model: Optional[str] = None, embed_pooling: Optional[str] = None):
         self._models = list(models)
+        self.embed_pooling = embed_pooling_setting(embed_pooling)
         self.prefix_cache = bool(prefix_cache)
         self.speculative = int(speculative)  # drafts per decode step (engine/speculative.py); 0: off
         if not 0 <= self.speculative <= 7:
@@ -326,9 +358,11 @@ class EngineBackend(Backend):
         cfg = get_config(model)
         ckpt = checkpoint_for(model)
         info = cfg.as_dict() | ({"checkpoint": ckpt} if ckpt else {"weights": "random-init"})
+        info["embedding_length"] = int(cfg.d_model)  # the floats of an /api/embed vector
         out = {"details": {"family": cfg.family or cfg.name.split(":")[0],
                            "parameter_size": f"{cfg.n_params() / 1e9:.1f}B",
-                           "quantization_level": QUANT_LEVEL[self.weight_dtype], "format": "cain-packed"},
+                           "quantization_level": QUANT_LEVEL[self.weight_dtype], "format": "cain-packed",
+                           "embed_pooling": self.embed_pooling},
                "model_info": info}
         if self.speculative:
             out["details"]["speculative"] = self.speculative_label
@@ -378,6 +412,10 @@ class EngineBackend(Backend):
         stops = j.options.get("stop") if j.options else None
         dec = eng.text_decoder(bool(j.format), bool(stops))
         return StopStreamer(eng, stops, dec) if stops else StreamDecoder(dec)
+
+    def embed(self, model: str, job: EmbedJob, cb=None) -> None:
+        src = cb if cb is not None else self.engine(model)
+        job.result = src.embed(job.inputs, pooling=self.embed_pooling, normalize=True, truncate=job.truncate)
 
     def run(self, model: str, jobs: List[Job]) -> None:
         eng = self.engine(model)
@@ -443,6 +481,15 @@ class EngineBackend(Backend):
                     pending.append(q.get_nowait())
                 except queue.Empty:
                     break
+            # the second job kind: embeddings run here, between graph chunks, on free slots (the queue is only read
+            # while a slot is free: with none they wait, as a generate job does); a failure is that request's own
+            for j in [j for j in pending if isinstance(j, EmbedJob)]:
+                try:
+                    self.embed(model, j, cb)
+                except Exception as exc:  # noqa: BLE001
+                    j.error = exc
+                j.done.set()
+            pending = [j for j in pending if not isinstance(j, EmbedJob)]
             try:
                 self._cb_iteration(model, eng, cb, tok, live, pending)
             except Exception as exc:  # noqa: BLE001 - fail every request in flight, start a fresh batch
@@ -574,6 +621,33 @@ class FakeBackend(Backend):
     def max_batch(self, model: str) -> int:
         return 8
 
+    EMBED_DIM = 64
+
+    def model_info(self, model: str) -> Dict[str, Any]:
+        return {"details": {"embed_pooling": self.embed_pooling}, "model_info": {"embedding_length": self.EMBED_DIM}}
+
+    def embed(self, model: str, job: EmbedJob, cb=None) -> None:
+        """A deterministic unit vector per input, seeded by the text alone; inputs beyond 2048 synthetic tokens count
+        as over the context."""
+        import hashlib
+
+        import numpy as np
+
+        from ..engine.engine import EmbedResult
+        from ..models.tokenizer import SyntheticTokenizer
+
+        if self.fail:
+            raise RuntimeError("fake backend failure")
+        tok, ctx, out = SyntheticTokenizer(32000), 2048, []
+        for text in job.inputs:
+            n = max(1, len(tok.encode(text)))
+            if n > ctx and not job.truncate:
+                raise ValueError(f"input of {n} tokens exceeds the context ({ctx}) and truncate is off")
+            seed = int.from_bytes(hashlib.sha256(text.encode("utf-8")).digest()[:8], "little")
+            v = np.random.default_rng(seed).standard_normal(self.EMBED_DIM)
+            out.append(EmbedResult((v / np.linalg.norm(v)).tolist(), min(n, ctx), n > ctx))
+        job.result = out
+
     def run(self, model: str, jobs: List[Job]) -> None:
         from ..engine.engine import GenResult
         from ..models.tokenizer import SyntheticTokenizer
@@ -640,7 +714,7 @@ class Scheduler:
             batch = [first]
             deadline = time.perf_counter() + self.window
             cap = self.backend.max_batch(model)
-            while len(batch) < cap:
+            while len(batch) < cap and not isinstance(first, EmbedJob):
                 rem = deadline - time.perf_counter()
                 if rem <= 0:
                     break
@@ -648,12 +722,23 @@ class Scheduler:
                     batch.append(q.get(timeout=rem))
                 except queue.Empty:
                     break
+            # static batches: an embed job runs on its own, between two batches (one that arrived inside a batch's
+            # window right after that batch)
+            embeds = [j for j in batch if isinstance(j, EmbedJob)]
+            batch = [j for j in batch if not isinstance(j, EmbedJob)]
             try:
-                self.backend.run(model, batch)
+                if batch:
+                    self.backend.run(model, batch)
             except BaseException as exc:  # noqa: BLE001 - reported per job
                 for j in batch:
                     j.error = exc
             for j in batch:
+                j.done.set()
+            for j in embeds:
+                try:
+                    self.backend.embed(model, j)
+                except BaseException as exc:  # noqa: BLE001 - reported to this request
+                    j.error = exc
                 j.done.set()
 
 
@@ -728,6 +813,10 @@ class OllamaHandler(BaseHTTPRequestHandler):
             return self._generate(body, chat=False)
         if self.path == "/api/chat":
             return self._generate(body, chat=True)
+        if self.path == "/api/embed":
+            return self._embed(body, legacy=False)
+        if self.path == "/api/embeddings":
+            return self._embed(body, legacy=True)
         if self.path == "/api/show":
             m = body.get("model") or body.get("name")
             if m not in self.scheduler.backend.models():
@@ -738,6 +827,49 @@ class OllamaHandler(BaseHTTPRequestHandler):
             ok = m in self.scheduler.backend.models()
             return self._send_json(200 if ok else 404, {"status": "success"} if ok else {"error": "unknown model"})
         return self._send_json(404, {"error": "not found"})
+
+    def _embed(self, body: Dict[str, Any], legacy: bool) -> None:
+        """``POST /api/embed`` ({"model", "input": str | [str], "truncate"}; ``options`` and ``keep_alive`` accepted and
+        ignored) and the older ``POST /api/embeddings`` ({"model", "prompt"}): the inputs embedded raw, L2-normalised
+        on both routes, pooled as the server is set (``--embed-pooling``).  A missing or unknown model answers as
+        ``/api/generate`` does (400 / 404)."""
+        t0 = time.perf_counter_ns()
+        model = body.get("model")
+        if not model:
+            return self._send_json(400, {"error": "model is required"})
+        if legacy:
+            inputs: Any = body.get("prompt", "")
+            if not isinstance(inputs, str):
+                return self._send_json(400, {"error": "prompt must be a string"})
+            inputs = [inputs]
+        else:
+            inputs = body.get("input", [])
+            inputs = [inputs] if isinstance(inputs, str) else inputs
+            if not isinstance(inputs, list) or any(not isinstance(x, str) for x in inputs):
+                return self._send_json(400, {"error": "input must be a string or a list of strings"})
+        truncate = body.get("truncate", True)
+        if not isinstance(truncate, bool):
+            return self._send_json(400, {"error": "truncate must be true or false"})
+        if model not in self.scheduler.backend.models():
+            return self._send_json(404, {"error": f"model '{model}' not found, try pulling it first"})
+        engines = getattr(self.scheduler.backend, "engines", {})
+        loaded = model in engines  # (else this request pays the model's load, and reports it)
+        job = EmbedJob(model, list(inputs), truncate)
+        if inputs:
+            self.scheduler.submit(job)
+            job.done.wait()
+        else:
+            job.result = []
+        if isinstance(job.error, ValueError):  # an over-long input with truncate: false
+            return self._send_json(400, {"error": str(job.error)})
+        if job.error is not None:
+            return self._send_json(500, {"error": str(job.error)})
+        if legacy:
+            return self._send_json(200, {"embedding": job.result[0].embedding})
+        load_ns = 0 if loaded else int(getattr(engines.get(model), "load_duration_ns", 0))
+        return self._send_json(200, {"model": model, "embeddings": [r.embedding for r in job.result],
+                                     "total_duration": int(time.perf_counter_ns() - t0), "load_duration": load_ns,
+                                     "prompt_eval_count": sum(r.prompt_eval_count for r in job.result)})
 
     def _generate(self, body: Dict[str, Any], chat: bool) -> None:
         model = body.get("model")
@@ -945,6 +1077,9 @@ def main(argv: Optional[List[str]] = None) -> None:
     ap.add_argument("--checkpoint", action="append", metavar="TAG=PATH",
                     help="serve a Hugging Face checkpoint directory or GGUF file under TAG (repeatable; models/hf.py); "
                          "PATH 'ollama' takes the blob a local Ollama store keeps for TAG")
+    ap.add_argument("--embed-pooling", choices=list(EMBED_POOLINGS), default=None,
+                    help="/api/embed and /api/embeddings: the position(s) an embedding is pooled over (default: "
+                         "CAIN_EMBED_POOLING, else last)")
     ap.add_argument("-v", "--verbose", action="store_true")
     ns = ap.parse_args(argv)
     ck_tags = register_checkpoints(ns.checkpoint)
@@ -960,11 +1095,12 @@ def main(argv: Optional[List[str]] = None) -> None:
     draft = _draft_model_arg(ns.draft_model, ns.speculative)
     if ns.backend == "fake":
         be: Backend = FakeBackend(models, tokens_per_s=ns.fake_tok_s, prefill_s=ns.fake_prefill_s)
+        be.embed_pooling = embed_pooling_setting(ns.embed_pooling)
     else:
         be = EngineBackend(models, device=ns.device, max_batch=ns.max_batch, max_context=ns.max_context,
                            backend=ns.backend, preload=ns.preload, trace_dir=ns.trace_dir, weight_dtype=ns.weights,
                            continuous=not ns.static_batching, kv_dtype=ns.kv, prefix_cache=ns.prefix_cache,
-                           speculative=ns.speculative, draft_model=draft)
+                           speculative=ns.speculative, draft_model=draft, embed_pooling=ns.embed_pooling)
     srv = make_server(be, ns.host, ns.port, ns.batch_window_ms, ns.verbose)
     print(f"[serve] Ollama-compatible API on http://{ns.host}:{srv.server_address[1]} models={models}", flush=True)
     try:
@@ -1026,3 +1162,44 @@ def generate_main(argv: Optional[List[str]] = None) -> None:
             raise SystemExit(f"--format {ns.format}: {exc}")
     be.run(ns.model, [job])
     print(json.dumps(_result_json(job)))
+
+
+def embed_main(argv: Optional[List[str]] = None) -> None:
+    """``python -m cain_amd embed --model M (--input TEXT ... | --file F)``: the texts' embeddings (--file: one per
+    non-empty line) from a local engine, one JSON line on stdout."""
+    ap = argparse.ArgumentParser(prog="python -m cain_amd embed")
+    ap.add_argument("--model", required=True)
+    ap.add_argument("--weights", choices=list(QUANT_LEVEL), default="bf16")
+    ap.add_argument("--kv", choices=["bf16", "fp8"], default="bf16")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--backend", choices=["hip", "torch"], default=None)
+    ap.add_argument("--max-batch", type=int, default=16)
+    ap.add_argument("--max-context", type=int, default=2048)
+    ap.add_argument("--checkpoint", metavar="PATH", help="a Hugging Face checkpoint directory, served as --model")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--input", nargs="+", metavar="TEXT")
+    src.add_argument("--file", metavar="F", help="one input per non-empty line")
+    ap.add_argument("--pooling", choices=list(EMBED_POOLINGS), default="last")
+    ap.add_argument("--no-normalize", action="store_true", help="the pooled vector as it is, not L2-normalised")
+    ap.add_argument("--no-truncate", action="store_true", help="refuse an input beyond the context instead of cutting it")
+    ns = ap.parse_args(argv)
+    if ns.checkpoint:
+        register_checkpoints([f"{ns.model}={ns.checkpoint}"])
+    if ns.file:
+        with open(ns.file, encoding="utf-8") as fh:
+            inputs = [ln.rstrip("\n") for ln in fh if ln.strip()]
+    else:
+        inputs = list(ns.input)
+    be = EngineBackend([ns.model], device=ns.device, max_batch=ns.max_batch, max_context=ns.max_context,
+                       backend=ns.backend, weight_dtype=ns.weights, kv_dtype=ns.kv)
+    eng = be.engine(ns.model)
+    try:
+        t0 = time.perf_counter()
+        res = eng.embed(inputs, pooling=ns.pooling, normalize=not ns.no_normalize, truncate=not ns.no_truncate)
+        dt = time.perf_counter() - t0
+    except ValueError as exc:
+        raise SystemExit(f"embed: {exc}")
+    n = sum(r.prompt_eval_count for r in res)
+    print(json.dumps({"model": ns.model, "weights": ns.weights, "pooling": ns.pooling, "dim": int(eng.cfg.d_model),
+                      "inputs": len(inputs), "prompt_eval_count": n, "tok_per_s": n / dt if dt > 0 else 0.0,
+                      "embeddings": [r.embedding for r in res]}))
